@@ -14,6 +14,10 @@ are global and combined with dist.all_reduce(MIN) over RCCL.
 
 Prints one JSON line (rank 0).  `value` counts the node-evals the GPUs actually performed
 (device counters; first-hit early exit skips (tape, model-block) pairs above a found hit).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line; ``--full`` adds the legs
+that take runs of their own (CPU baseline, drop-in, fork stream, z3 calls avoided, keccak service);
+``--dump-outputs DIR`` writes the last timed step's first hits to ``DIR/first_hit.npy``.
 """
 from __future__ import annotations
 
@@ -89,14 +93,22 @@ def parse():
     p.add_argument("--tapes", type=int, default=None)
     p.add_argument("--models", type=int, default=None, help="candidate models per GPU")
     p.add_argument("--seed", type=int, default=None)
-    p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs that take runs of their own (1 GPU): the CPU "
+                        "baseline, and the drop-in, fork-stream, z3-calls-avoided and keccak legs.  A plain run "
+                        "sets up, warms up, times --steps steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed, the per-tape first-hit index "
+                        "(-1 = no hit), to DIR/first_hit.npy (float64)")
+    p.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU-baseline sample time")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                    help="nccl (= RCCL over xGMI, the product path); gloo stages the 4N-byte reduce through "
                         "the host and lets a 1-GPU box rehearse N>1 with --device 0")
     p.add_argument("--device", type=int, default=None, help="override LOCAL_RANK -> device mapping (rehearsal)")
     p.add_argument("--no-hoist", action="store_true", help="c3/c4/c5: lower without batch-level hoisting")
-    p.add_argument("--no-dropin", action="store_true", help="skip the drop-in leg (ModelCache at N<=256, M<=100)")
+    p.add_argument("--no-dropin", action="store_true",
+                   help="--full without the drop-in legs (ModelCache at N<=256, M<=100)")
     p.add_argument("--no-early-exit", action="store_true", help="diagnostic: evaluate every (tape, model) pair")
     p.add_argument("--context", action="store_true",
                    help="drive the GPUs through one multi-device mq_ctx even at --gpus 1 (in-library RCCL with "
@@ -719,12 +731,6 @@ def main():
     for _ in range(args.warmup):
         step()
     sync_all()
-    # correctness gate on the benchmark workload itself (planted first hits)
-    got = best.cpu().numpy()
-    ok = bool((got == expected).all())
-    if not ok:
-        bad = np.flatnonzero(got != expected)
-        print(f"[rank {rank}] first-hit mismatch on {len(bad)} tapes, e.g. {bad[:5]}", file=sys.stderr)
 
     # where the batch ran (after a launch): tapes on the P / G assembly interpreters vs the HIP C++
     # kernels, hoisted columns on G / the keccak and bit-gather column kernels / the C++ column kernel
@@ -762,6 +768,17 @@ def main():
         dist.barrier()
     t_end = time.perf_counter()
     elapsed = t_end - t0
+    # what the last timed step computed: the per-tape first hit (global index, -1 = none).  It is
+    # the correctness gate on the benchmark workload itself (planted first hits) and what
+    # --dump-outputs writes
+    got = best.cpu().numpy()
+    ok = bool((got == expected).all())
+    if not ok:
+        bad = np.flatnonzero(got != expected)
+        print(f"[rank {rank}] first-hit mismatch on {len(bad)} tapes, e.g. {bad[:5]}", file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "first_hit.npy"), got.astype(np.float64))
     pairs, node_evals, alg_ops = ev.counters(reset=True)
     ctx_attr = None
     if mode == "context":
@@ -865,7 +882,8 @@ def main():
         }
         if oracle:
             out["engine"] = "oracle (CPU rehearsal of the protocol; not a measurement)"
-        if n_gpus == 1 and not args.no_cpu_baseline and not oracle:
+        # everything below takes runs of its own: only with --full
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and not oracle:
             if getattr(tb, "columns", None) is not None:
                 # the reference evaluates every conjunction in full per model: time the oracle on
                 # the same conjunctions lowered without hoisting
@@ -875,7 +893,7 @@ def main():
                 cb = cpu_baseline(tb, mb, args.cpu_seconds)
             out["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample", "single_core_value", "host")}
             out["gpu_over_cpu"] = out["value"] / cb["value"]
-        if n_gpus == 1 and not args.no_dropin and not oracle:
+        if args.full and n_gpus == 1 and not args.no_dropin and not oracle:
             out["dropin"] = dropin_leg(ev)
             out["dropin_stream"] = dropin_stream_leg(ev)
             out["dropin_stream_z3stub"] = dropin_stream_z3stub_leg(ev)

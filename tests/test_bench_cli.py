@@ -116,6 +116,45 @@ def test_two_rank_line_under_gloo_with_the_oracle_engine():
     assert line["engine"].startswith("oracle")
 
 
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run times its steps and prints the line; the legs that take runs of their own
+    (CPU baseline, drop-in, fork stream, z3 calls avoided, keccak) wait for --full."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_last_steps_first_hits_the_same_every_run(tmp_path):
+    """--dump-outputs with the oracle answering for the GPU: first_hit.npy holds the per-tape first
+    hit of the last timed step in float64, equal to the workload's planted hits and identical from
+    run to run with the same arguments; --warmup 0 is honoured and --steps sets the timed steps."""
+    import json
+    import numpy as np
+    from mythril_amd.synth import c2_workload
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run, (steps, warmup) in enumerate(((3, 0), (1, 1))):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--engine", "oracle",
+                            "--tapes", "40", "--models", "64", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["parity_ok"] is True
+        assert line["ms_per_step"] > 0
+        assert "cpu_baseline" not in line and "dropin" not in line and "keccak_service" not in line
+        assert sorted(p.name for p in d.iterdir()) == ["first_hit.npy"]
+        dumps.append(np.load(d / "first_hit.npy"))
+    _, _, expected = c2_workload(40, 64, seed=2)
+    for a in dumps:
+        assert a.dtype == np.float64 and a.shape == (40,)
+        assert np.array_equal(a, expected.astype(np.float64))
+    assert (dumps[0] >= 0).any() and (dumps[0] < 0).any()
+
+
 @pytest.mark.parametrize("gpus", [1, 2])
 def test_context_mode_line_is_attributable_with_the_oracle_engine(gpus):
     """One process driving N devices (--context, the way single-process Mythril would,

@@ -13,10 +13,10 @@ if [ "$PART" = "lines" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1 || { tail -30 "$OUT/pytest_gpu.log"; exit 11; }
   tail -1 "$OUT/pytest_gpu.log"
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1 || { tail "$OUT/smoke.txt"; exit 12; }
-  timeout -k 10 600 python -u bench.py > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err" || { tail "$OUT/bench_c2.err"; exit 13; }
+  timeout -k 10 600 python -u bench.py --full > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err" || { tail "$OUT/bench_c2.err"; exit 13; }
   line "$OUT/bench_c2.json" c2
   for c in c3 c4 c5; do
-    timeout -k 10 600 python -u bench.py --config $c --steps 5 --warmup 2 --no-dropin > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail "$OUT/bench_$c.err"; exit 14; }
+    timeout -k 10 600 python -u bench.py --config $c --steps 5 --warmup 2 --full --no-dropin > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail "$OUT/bench_$c.err"; exit 14; }
     line "$OUT/bench_$c.json" $c
   done
 elif [ "$PART" = "prof" ]; then

@@ -16,7 +16,7 @@ if [ "$KEXPR" != "none" ]; then
 fi
 for c in $CFGS; do
   if [ "$c" = "c2full" ]; then
-    timeout -k 10 600 python -u bench.py > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 4; }
+    timeout -k 10 600 python -u bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 4; }
     f=$O/bench_c2.json
   else
     timeout -k 10 600 python -u bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline --no-dropin > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 4; }

@@ -7,7 +7,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 bash tools/gpu_iter.sh $TAG "$SEL" "c3 c4 c5" "" || exit $?
 timeout -k 10 300 python -u bench.py --gpus 1 --context --steps 3 --warmup 1 --no-cpu-baseline --no-dropin > $O/bench_ctx1.json 2> $O/bench_ctx1.err || { tail -20 $O/bench_ctx1.err; exit 5; }
 python -c "import json; d=json.loads(open('$O/bench_ctx1.json').read().strip().splitlines()[-1]); print('ctx1', round(d['ms_per_step'],3), d['per_rank'])"
-timeout -k 10 900 python -u bench.py > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 6; }
+timeout -k 10 900 python -u bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 6; }
 python - $O/bench_c2.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

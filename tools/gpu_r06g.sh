@@ -7,7 +7,7 @@ tail -1 $O/pytest.txt
 timeout -k 10 200 python -u tools/stream_loop.py 1 16 300 > $O/loop_1_16.json 2>&1 || exit 4
 timeout -k 10 200 python -u tools/stream_loop.py 16 100 100 > $O/loop_16_100.json 2>&1 || exit 5
 cat $O/loop_1_16.json $O/loop_16_100.json
-timeout -k 10 900 python -u bench.py > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 6; }
+timeout -k 10 900 python -u bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || { tail -20 $O/bench_c2.err; exit 6; }
 python - $O/bench_c2.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
