@@ -201,8 +201,10 @@ typedef struct mq_model_batch {
 /* ------------------------------------------------------------------ statistics */
 typedef struct mq_stats {
   double kernel_ms;        /* device time of the evaluation kernels (HIP events) */
-  double node_evals;       /* sum over evaluated (tape, model) pairs of |tape| nodes */
-  double alg_ops;          /* algorithmic 32-bit VALU ops (SURVEY §8(d) cost table) */
+  double node_evals;       /* sum over evaluated (= decided) (tape, model) pairs of |tape| nodes,
+                              whether or not a wave left the tape early at a bail point */
+  double alg_ops;          /* algorithmic 32-bit VALU ops (SURVEY §8(d) cost table) executed:
+                              ops a wave skipped at a bail point are not counted */
   int64_t pairs_evaluated; /* (tape, model) pairs actually evaluated (early exit skips the rest) */
   int32_t n_hits;
   int32_t n_unsupported;
@@ -422,6 +424,16 @@ int mq_tape_compile_info_g(const mq_tape_batch* batch, int32_t t, int32_t* depth
    words[cap]; *n_words = its length (also when cap is too small, then nothing is copied).
    Returns 0, MQ_ERR_ARG, or MQ_ERR_TAPE when the tape does not compile. */
 int mq_tape_program(const mq_tape_batch* batch, int32_t t, uint32_t* words, int32_t cap, int32_t* n_words);
+
+/* Host-only: tape t compiled as a verdict tape for the G assembly interpreter's stack (what an
+   upload builds for it: bail points and all, unlike mq_tape_compile_info_g, which reports the
+   column-program compile): the program G would run -- the spilled variant when the plain program
+   needs more than kQsaStackG slots, else the plain one -- into words[cap], *n_words its length (also
+   when cap is too small, then nothing is copied), *depth_g / *n_temps_g its stack slots and LDS
+   temps, *spilled whether it is the spilled variant (each may be NULL).  Returns 0, MQ_ERR_ARG,
+   or MQ_ERR_TAPE when the tape does not compile. */
+int mq_tape_program_g(const mq_tape_batch* batch, int32_t t, uint32_t* words, int32_t cap, int32_t* n_words,
+                      int32_t* depth_g, int32_t* n_temps_g, int32_t* spilled);
 
 /* Library version string. */
 const char* mq_version(void);

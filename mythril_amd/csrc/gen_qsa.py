@@ -1236,6 +1236,14 @@ def make_handlers(variant, pfx):
             acc.append((key, list(body), bool(pre)))
 
     H(("END",), [f"s_branch {pfx}_tape_end"], tail=False, reads_stack=False)
+    if not G:
+        # bail point of a conjunction spine (gprog.h G_BAIL; imm = the §8(d) ops of the rest of
+        # the program): B(0) is the conjunction so far.  No valid lane left: the verdict is false
+        # for the whole wave, the tape ends here (the frame takes the skipped ops off the ops
+        # counter; its wait drains the entry and constant prefetches in flight).  Right after END:
+        # s_branch reaches the frame only from the first handlers.
+        H(("BAIL",), [f"s_and_b64 s[34:35], {B(0)}, s[62:63]", f"s_cbranch_scc0 {pfx}_bail_out"] + NEXT_P
+          + [f"{pfx}_bail_out:", "s_mov_b32 s36, s17", f"s_branch {pfx}_tape_bail"], tail=False, reads_stack=False)
     if G:
         # a program whose last push (PUSH_MEM) may still be in flight (mq_api.cpp final pass):
         # the tape end waits for it here, so the column store needs no vector wait of its own
@@ -1981,7 +1989,13 @@ def frame(variant, pfx, handlers, subs):
         "s_mov_b32 s78, s84",
         "s_mov_b32 s79, s87",
         "s_mov_b32 s100, s82",
-    ] + NEXT_P) + [
+    ] + NEXT_P) + ([] if G else [
+        # a BAIL handler left the tape early: s36 = the ops it skipped (the tape end adds the
+        # whole tape's: the ops counter is of executed ops; pairs and nodes count decided pairs)
+        f"{pfx}_tape_bail:",
+        "s_sub_u32 s44, s44, s36",
+        "s_subb_u32 s45, s45, 0",
+    ]) + [
         f"{pfx}_tape_end:",
         "s_waitcnt lgkmcnt(0)",
     ] + (prof_point("F_ENDW") if G else []) + [

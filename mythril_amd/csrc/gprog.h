@@ -86,6 +86,11 @@ enum GOp : uint32_t {
   G_UFK = 33,        // S[d-1] = S[d-1] & entries whose key chunk k equals S[d]; next word = k
   G_UFKV = 34,       // S[d] = value of the first entry in the set S[d], else the else value;
                      // next word = result width
+  // bail point of a verdict tape's conjunction spine (tape_compiler.cpp): d = 0; next word = the
+  // SURVEY §8(d) algorithmic ops of everything after it in the program.  If no valid lane of the
+  // wave has B(0) set the program's result is false for the whole wave and the rest may be
+  // skipped; a kernel may treat it as a no-op
+  G_BAIL = 35,
   G_NUM_OPS = 64
 };
 
@@ -97,7 +102,7 @@ enum GOp : uint32_t {
 
 // ops followed by a second instruction word (imm2)
 GPROG_HD static inline bool has_imm2(uint32_t op) {
-  return op == 56 || op == 57 || op == 58 || op == 60 || op == 61 || op == 32 || op == 33 || op == 34;
+  return op == 56 || op == 57 || op == 58 || op == 60 || op == 61 || op == 32 || op == 33 || op == 34 || op == 35;
 }
 
 static inline uint32_t gword(uint32_t op, uint32_t d, uint32_t imm) { return op | (d << 8) | (imm << 12); }

@@ -315,6 +315,8 @@ static constexpr int64_t kDenseMaxE = 16;
 
 // the assembly interpreter keeps temps in LDS (2 KB per temp per wave, 4 waves per workgroup)
 static constexpr int kQsaMaxTemps = 16;
+// bail points (gprog.h G_BAIL) go on the tapes whose variables P preloads: only P takes them
+static_assert(CompileLimits{}.bail_var_limit == kQsaVars, "bail points are for the tapes P can run");
 
 // HIP C++ interpreter variants (qs_kernels.hip launch_qs): limbs per stack slot and whether the
 // variant carries the interpreted-keccak handler.  Kind 0 (L = 8) is where 256-bit tapes the
@@ -770,6 +772,23 @@ int mq_tape_program(const mq_tape_batch* tb, int32_t t, uint32_t* words, int32_t
   if (!c.supported) return MQ_ERR_TAPE;
   *n_words = (int32_t)c.prog.size();
   if (words && cap >= (int32_t)c.prog.size()) std::memcpy(words, c.prog.data(), c.prog.size() * sizeof(uint32_t));
+  return MQ_OK;
+}
+
+int mq_tape_program_g(const mq_tape_batch* tb, int32_t t, uint32_t* words, int32_t cap, int32_t* n_words,
+                      int32_t* depth_g, int32_t* n_temps_g, int32_t* spilled) {
+  if (!tb || t < 0 || t >= tb->n_tapes || !n_words) return MQ_ERR_ARG;
+  CompileLimits lim;
+  lim.g_depth = kQsaStackG;
+  CompiledTape c = compile_tape(tb, t, lim);
+  if (!c.supported) return MQ_ERR_TAPE;
+  const bool alt = !c.prog_g.empty();
+  const std::vector<uint32_t>& pr = alt ? c.prog_g : c.prog;
+  *n_words = (int32_t)pr.size();
+  if (words && cap >= (int32_t)pr.size()) std::memcpy(words, pr.data(), pr.size() * sizeof(uint32_t));
+  if (depth_g) *depth_g = alt ? c.depth_g : c.depth;
+  if (n_temps_g) *n_temps_g = alt ? c.n_temps_g : c.n_temps;
+  if (spilled) *spilled = alt ? 1 : 0;
   return MQ_OK;
 }
 
@@ -1597,12 +1616,19 @@ static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTap
       if (++pc >= xprog.size()) return false;
       imm2 = xprog[pc];
     }
+    // a bail point is P's only (G drops the word: its pushes in flight and its program window
+    // make leaving mid-program a stage of its own); dropped, it leaves the fusions' view of
+    // the previous instruction untouched
+    if (op == G_BAIL && !P) continue;
     const size_t out_before = out.size();
     const bool after_const = prev_op == G_PUSH_CONST && (int)prev_d == d;
     int pushed_pre = -1;
     bool ok;
     switch (op) {
       case G_END: ok = word(QK_END, 0, -1, 0); break;
+      // P: an entry without a constant (an ordinary non-PF_ entry to the constant prefetch
+      // pass); its 32-bit immediate is the ops the rest of the program would cost
+      case G_BAIL: ok = d == 0 && word(QK_BAIL, 0, -1, imm2, true); break;
       case G_PUSH_VAR:
       case G_PUSH_VAR_B: {
         const bool b = op == G_PUSH_VAR_B;
@@ -3042,6 +3068,10 @@ static bool fc_match(const mq_ctx* c, const CompiledTape& x, std::vector<uint32_
         a.xf.push_back(FcXop{FX_SEXT | (imm << 8), w2, 0, 0});
       }
       a.w = w2;
+      continue;
+    }
+    if (op == G_BAIL) {   // (a flat conjunction is too cheap to carry one; skipped all the same)
+      pc++;
       continue;
     }
     if (has_imm2(op)) return false;
@@ -4706,7 +4736,10 @@ int mq_eval_tapes_first_hit(mq_ctx* c, mq_tapes* T, int32_t* out, mq_stats* stat
     stats->kernel_ms = ms;
     stats->pairs_evaluated = (int64_t)total[0];
     stats->node_evals = (double)total[1];
-    stats->alg_ops = (double)total[2];  // exact: per evaluated (tape, model) pair, the tape's cost
+    // executed ops: per evaluated (tape, model) pair the tape's cost, less what a wave skipped at
+    // a bail point (gprog.h G_BAIL) -- a utilisation's numerator, unlike pairs and node_evals,
+    // which count decided pairs whether a wave ran the whole tape or not
+    stats->alg_ops = (double)total[2];
     int hits = 0;
     for (int t = 0; t < T->n_tapes; t++) hits += out[t] >= 0;
     stats->n_hits = hits;

@@ -856,6 +856,7 @@ MQ_DEV bool run_tape(cu32p prog, const Ctx& cx) {
       case G_KECCAK:
         if constexpr (K) h_keccak<L>(cx, d, imm);
         break;
+      case G_BAIL: break;   // (a bail point: its second word was stepped over above; a no-op here)
       default: break;
     }
   }

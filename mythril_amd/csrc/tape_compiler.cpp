@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <tuple>
@@ -120,6 +121,8 @@ struct Fail {
 
 }  // namespace
 
+static double node_alg_ops(const mq_node* nd, int64_t i);
+
 CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLimits& lim) {
   CompiledTape out;
   const int64_t base = batch->tape_offsets[t];
@@ -130,6 +133,10 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
     return out;
   }
   const mq_node* nd = batch->nodes + base;
+  // conjunction spine with bail points (verdict tapes only; read per compile: tests flip it)
+  bool bail_on = !lim.value_root && std::getenv("MQ_NO_BAIL") == nullptr;
+  double bail_min_ops = kBailMinOps;
+  if (const char* e = std::getenv("MQ_BAIL_MIN_OPS")) bail_min_ops = std::max(1.0, std::atof(e));
   try {
     // ---------------------------------------------------------------- 1. validate, kinds, widths
     std::vector<Kind> kind(nn);
@@ -233,6 +240,9 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
     Builder B;
     B.reserve((size_t)nn * 2);
     std::vector<int> map(nn, -1);
+    // §8(d) cost of every boundary node, charged to the internal node it lowered to (a select's
+    // whole ite chain to its top): the sum over the internal DAG is tape_alg_ops
+    std::vector<double> icost;
     std::unordered_map<std::vector<uint32_t>, uint32_t, WordsHash> cmemo;  // constant dedup -> word offset
     auto konst = [&](int64_t i) -> int {
       const mq_node& n = nd[i];
@@ -288,6 +298,9 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
         case MQ_OP_CONST: r = konst(i); break;
         case MQ_OP_VAR: {
           if (n.a > (uint32_t)kMaxImm) throw Fail{"var index too large"};
+          // only the P interpreter takes bail points, and it runs tapes over its preloaded
+          // variables only: any other tape keeps today's program
+          if (n.a >= (uint32_t)lim.bail_var_limit) bail_on = false;
           INode x = mk(w == 0 ? G_PUSH_VAR_B : G_PUSH_VAR, w, {}, n.a);
           x.leaf = true;
           r = B.add(x);
@@ -368,7 +381,14 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
           throw Fail{"unsupported opcode"};
       }
       map[i] = r;
+      if (r >= 0) {
+        if (icost.size() < B.nodes.size()) icost.resize(B.nodes.size(), 0.0);
+        icost[r] += std::max(0.0, node_alg_ops(nd, i));
+      }
     }
+    icost.resize(B.nodes.size(), 0.0);
+    double total_cost = 0;
+    for (double v : icost) total_cost += v;
     const int root = map[nn - 1];
     if (root < 0) throw Fail{"root lowered to nothing"};
 
@@ -560,9 +580,110 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
       prog.push_back(gword(g, d, n.imm));
       if (has_imm2(g)) prog.push_back(n.imm2);
     };
+    // Verdict tapes whose root is a conjunction: the root unit as a spine with bail points.
+    // The tree of single-use, un-hoisted AND nodes under the root is flattened into conjuncts
+    // c_0 .. c_{k-1}; c_0 is evaluated at slot 0, every other one at slot 1 and AND-ed into
+    // slot 0 (G_AND d = 1), so B(0) always holds the conjunction so far.  After conjunct i a
+    // G_BAIL carries the cost of everything behind it, when that is at least bail_min_ops and
+    // an EQ conjunct is among c_0 .. c_i.
+    // Order: conjuncts that are an EQ of bit-vector operands first, cheapest first (the only
+    // ones a whole wave of unrelated models fails together), the others as written -- unless
+    // that needs more stack slots than today's Sethi-Ullman order: then the conjunct today's
+    // order evaluates first stays first (with it at slot 0 the spine never needs more: every
+    // right operand of today's nesting sits at slot >= 1).  A tape that gets no bail point is
+    // emitted exactly as before.
+    auto emit_root = [&](int x) -> void {
+      const INode& rn = B.nodes[x];
+      if (!bail_on || rn.leaf || rn.gop != G_AND || hoist[x] || total_cost >= 4.0e9) {
+        emit_rec(emit_rec, x, 0);
+        return;
+      }
+      // the conjuncts as written (left to right) and in today's emission order (operand swaps)
+      std::vector<int> written, conj, ands;
+      auto flat = [&](auto& self, int y, bool today) -> void {
+        const INode& n = B.nodes[y];
+        const bool inner = !n.leaf && n.gop == G_AND && (y == x || (uses[y] == 1 && !hoist[y]));
+        if (!inner) {
+          (today ? conj : written).push_back(y);
+          return;
+        }
+        self(self, n.kid[today && swap[y] ? 1 : 0], today);
+        self(self, n.kid[today && swap[y] ? 0 : 1], today);
+        if (today) ands.push_back(y);
+      };
+      flat(flat, x, false);
+      flat(flat, x, true);
+      const size_t k = conj.size();
+      auto nd_of = [&](int c) { return (hoist[c] || B.nodes[c].leaf) ? 1 : need[c]; };
+      // cost of the nodes each conjunct is the first to evaluate (hoisted nodes ran before the
+      // root unit; a node shared with an earlier conjunct is charged there)
+      std::vector<char> seen(NI, 0);
+      auto first_cost = [&](int c) -> double {
+        double sum = 0;
+        std::vector<int> st{c};
+        while (!st.empty()) {
+          const int y = st.back();
+          st.pop_back();
+          if (seen[y] || hoist[y]) continue;
+          seen[y] = 1;
+          sum += icost[y];
+          for (int j = 0; j < B.nodes[y].nk; j++) st.push_back(B.nodes[y].kid[j]);
+        }
+        return sum;
+      };
+      auto own_cost = [&](int c) -> double {
+        std::fill(seen.begin(), seen.end(), 0);
+        return first_cost(c);
+      };
+      auto is_bv_eq = [&](int c) { return !hoist[c] && !B.nodes[c].leaf && B.nodes[c].gop == G_EQ && B.nodes[c].imm >= 1; };
+      std::vector<std::pair<double, int>> eqs;
+      std::vector<int> order, rest;
+      for (int c : written) {
+        if (is_bv_eq(c)) eqs.push_back({own_cost(c), c});
+        else rest.push_back(c);
+      }
+      std::stable_sort(eqs.begin(), eqs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+      for (const auto& e : eqs) order.push_back(e.second);
+      order.insert(order.end(), rest.begin(), rest.end());
+      int spine_need = nd_of(order[0]);
+      for (size_t i = 1; i < k; i++) spine_need = std::max(spine_need, nd_of(order[i]) + 1);
+      if (spine_need > need[x]) {
+        // today's first conjunct keeps slot 0 (the spine's need depends on the order only
+        // through which conjunct that is); the others follow in the new order
+        const int c0 = conj[0];
+        order.erase(std::find(order.begin(), order.end(), c0));
+        order.insert(order.begin(), c0);
+      }
+      // rem[i]: cost of everything after conjunct i (and its AND)
+      std::fill(seen.begin(), seen.end(), 0);
+      std::vector<double> step(k, 0.0), rem(k, 0.0);
+      for (size_t i = 0; i < k; i++) step[i] = first_cost(order[i]) + (i > 0 ? icost[ands[i - 1]] : 0.0);
+      for (size_t i = k - 1; i-- > 0;) rem[i] = rem[i + 1] + step[i + 1];
+      // a bail point pays only where a whole wave can have failed: once an EQ conjunct has run
+      std::vector<char> bail(k, 0);
+      bool any = false, eq_seen = false;
+      for (size_t i = 0; i + 1 < k; i++) {
+        eq_seen = eq_seen || is_bv_eq(order[i]);
+        bail[i] = eq_seen && rem[i] >= bail_min_ops;
+        any = any || bail[i];
+      }
+      if (!any) {
+        emit_rec(emit_rec, x, 0);
+        return;
+      }
+      for (size_t i = 0; i < k; i++) {
+        emit_rec(emit_rec, order[i], i == 0 ? 0 : 1);
+        if (i > 0) prog.push_back(gword(G_AND, 1, 0));
+        if (bail[i]) {
+          prog.push_back(gword(G_BAIL, 0, 0));
+          prog.push_back((uint32_t)std::llround(rem[i]));
+        }
+      }
+    };
     for (size_t u = 0; u < units.size(); u++) {
       int x = units[u];
-      emit_rec(emit_rec, x, 0);
+      if (x == root) emit_root(x);
+      else emit_rec(emit_rec, x, 0);
       // release temps whose last use was this unit (before allocating this unit's own slot)
       for (int r : refs[u])
         if (unit_of_last_use[r] == (int)u) free_slots.push_back(slot[r]);
@@ -608,12 +729,10 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
   return out;
 }
 
-double tape_alg_ops(const mq_tape_batch* batch, int32_t t) {
-  const int64_t base = batch->tape_offsets[t];
-  const int64_t nn = batch->tape_offsets[t + 1] - base;
-  const mq_node* nd = batch->nodes + base;
+// SURVEY §8(d) cost of node i of a tape (nd = the tape's first node); -1 for an unknown opcode
+static double node_alg_ops(const mq_node* nd, int64_t i) {
   double ops = 0;
-  for (int64_t i = 0; i < nn; i++) {
+  {
     const mq_node& n = nd[i];
     double L = nl_of(n.width);
     double La = (n.a < (uint32_t)i) ? nl_of(nd[n.a].width) : L;
@@ -679,6 +798,19 @@ double tape_alg_ops(const mq_tape_batch* batch, int32_t t) {
       default:
         return -1;
     }
+  }
+  return ops;
+}
+
+double tape_alg_ops(const mq_tape_batch* batch, int32_t t) {
+  const int64_t base = batch->tape_offsets[t];
+  const int64_t nn = batch->tape_offsets[t + 1] - base;
+  const mq_node* nd = batch->nodes + base;
+  double ops = 0;
+  for (int64_t i = 0; i < nn; i++) {
+    const double o = node_alg_ops(nd, i);
+    if (o < 0) return -1;
+    ops += o;
   }
   return ops;
 }

@@ -25,6 +25,11 @@ constexpr int kMaxWidth = 2048;   // widest value a tape may hold (64 limbs)
 constexpr double kKeccakOpsPerBlock = 24.0 * 2.0 * (55 + 24 + 55 + 1) + 34.0;
 static_assert(kKeccakOpsPerBlock == 6514.0, "keccak-f[1600] op count");
 
+// A bail point (gprog.h G_BAIL) is placed where at least this many §8(d) ops follow it in the
+// program (MQ_BAIL_MIN_OPS overrides): taking one costs a dispatch, about ten scalar
+// instructions, so it must not split runs of one-op Bool conjuncts.
+constexpr double kBailMinOps = 64;
+
 struct CompiledTape {
   bool supported = false;
   std::string why;               // reason when unsupported
@@ -60,6 +65,13 @@ struct CompileLimits {
   int remat_max_nodes = 3;    // shared sub-terms up to this many cheap nodes are re-evaluated
   int g_depth = 0;            // > 0: also build prog_g for a stack of this many slots
   bool value_root = false;    // column program: any BV/Bool root, its value is the result
+  // conjunction spine and bail points (gprog.h G_BAIL) only for tapes whose variables all have
+  // an index below this: the P interpreter's preloaded variables (gen_qsa.py NV).  The G
+  // interpreter drops the word, and the spine's conjunct order alone measured a hair slower
+  // there (C3 16.25 against 16.16 ms), so its tapes keep their programs.  (The index is all
+  // the compiler knows: a tape over variables 0-7 that P cannot run -- an op it lacks, more than
+  // its six slots -- still gets the spine, and G runs it with the words dropped.)
+  int bail_var_limit = 8;
 };
 
 // Compile tape t of the batch. n_funcs/funcs describe the model function table (result

@@ -86,6 +86,7 @@ def load_library(path: str = LIB_PATH):
         L.mq_tapes_column_keccak_predicates.argtypes = [P, C.POINTER(C.c_int32)]
         L.mq_tape_compile_info_g.argtypes = [C.POINTER(MqTapeBatch), C.c_int32] + [C.POINTER(C.c_int32)] * 3
         L.mq_tape_program.argtypes = [C.POINTER(MqTapeBatch), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_int32)]
+        L.mq_tape_program_g.argtypes = [C.POINTER(MqTapeBatch), C.c_int32, C.POINTER(C.c_uint32), C.c_int32] + [C.POINTER(C.c_int32)] * 4
         L.mq_tapes_upload_dag.argtypes = [P, C.POINTER(MqDagBatch), C.POINTER(P), C.POINTER(C.c_int32)]
         L.mq_dag_expand.argtypes = [C.POINTER(MqDagBatch), C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]
         L.mq_models_shard.argtypes = [C.POINTER(MqModelBatch), C.c_int64, C.c_int64, C.POINTER(MqModelBatch), C.POINTER(P)]
@@ -163,6 +164,19 @@ def tape_program(tb: TapeBatch, t: int) -> np.ndarray:
     out = np.zeros(n.value, np.uint32)
     _check(L.mq_tape_program(C.byref(s), t, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)), "tape_program")
     return out
+
+
+def tape_program_g(tb: TapeBatch, t: int):
+    """Host-only: tape t compiled as a verdict tape for the G assembly interpreter's stack
+    (``mq_tape_program_g``): (program words, depth, LDS temps, whether it is the spilled variant)."""
+    L = load_library()
+    s, keep = as_tape_batch(tb)
+    n, d, nt, sp = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    _check(L.mq_tape_program_g(C.byref(s), t, None, 0, C.byref(n), None, None, None), "tape_program_g")
+    out = np.zeros(n.value, np.uint32)
+    _check(L.mq_tape_program_g(C.byref(s), t, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n),
+                               C.byref(d), C.byref(nt), C.byref(sp)), "tape_program_g")
+    return out, d.value, nt.value, bool(sp.value)
 
 
 def shard_models(mb: ModelBatch, lo: int, hi: int) -> ModelBatch:
