@@ -230,6 +230,46 @@ const char* mq_strerror(int code);
    n_models may be 0 (an empty model-axis shard: every tape reports MQ_NO_HIT). */
 int mq_models_upload(mq_ctx* ctx, const mq_model_batch* models);
 
+/* Derived upload: "these models are those models, patched" (the candidate generator's batches:
+   every generated candidate is a cached model's rows with a handful of bits changed).  The
+   variable rows of the K derived models are expanded on the device from the n_base explicit
+   models and a few (row, keep, bits) words, so nothing of size rows x K crosses the bus. */
+typedef struct mq_row_patch { uint32_t row, keep, bits; } mq_row_patch;   /* w = (w & keep) | bits */
+typedef struct mq_row_floor { uint32_t row0, n_limbs, minimum; } mq_row_floor;
+                              /* if limbs 1..n_limbs-1 are all 0 and limb0 < minimum: limb0 = minimum */
+typedef struct mq_derivation {
+  int64_t n_base;                /* leading models given explicitly (the LRU), >= 0 */
+  const uint32_t* base_words;    /* [rows * n_base] SoA, same row order as mq_model_batch.var_words */
+  int64_t n_derived;             /* K generated models, global indices index_base + n_base + k */
+  const int32_t* src;            /* [K] base model each one copies; -1 = all-zero rows */
+  int32_t n_blocks;              /* blocks = contiguous candidate ranges sharing one patch */
+  const int64_t* block_start;    /* [n_blocks+1], block_start[0] == 0, block_start[n_blocks] == K */
+  const int64_t* patch_ptr;      /* [n_blocks+1] into patches: at most one patch per (block, row) */
+  const mq_row_patch* patches;
+  const int64_t* floor_ptr;      /* [n_blocks+1] into floors; floors apply after the block's patches */
+  const mq_row_floor* floors;
+} mq_derivation;
+
+/* Host-only (no device needed): MQ_OK when `d` is a well-formed derivation of `models`
+   (n_base + n_derived == models->n_models, src[k] < n_base, patch rows < rows, floor rows
+   row0 + n_limbs <= rows with n_limbs >= 1, block_start / patch_ptr / floor_ptr monotone from 0),
+   else MQ_ERR_ARG.  mq_models_upload_derived runs it before it touches the device. */
+int mq_derivation_check(const mq_model_batch* models, const mq_derivation* d);
+
+/* Replace the candidate set with models [0, n_base) given by d->base_words followed by the K
+   derived ones.  `models` describes all M = n_base + K models exactly as for mq_models_upload
+   (widths, the complete host-built function CSR, else values, index_base) except var_words,
+   which is ignored and may be NULL.  Afterwards the context is indistinguishable from
+   mq_models_upload of the fully materialised batch.  A malformed derivation answers MQ_ERR_ARG
+   and leaves the resident models as they were.  Single-device contexts only: a multi-device
+   context answers MQ_ERR_ARG (the caller materialises the rows and uses mq_models_upload). */
+int mq_models_upload_derived(mq_ctx* ctx, const mq_model_batch* models, const mq_derivation* d);
+
+/* Diagnostic: the resident variable rows, [rows * M] words, after masking; n_words must be
+   rows * M.  Single-device contexts only (MQ_ERR_ARG otherwise); MQ_ERR_NO_MODELS before an
+   upload. */
+int mq_models_download_vars(mq_ctx* ctx, uint32_t* out, int64_t n_words);
+
 /* Host-only (no device needed): candidates [lo, hi) of `models` as a batch of their own, with
    index_base + lo — exactly the shard device g of a multi-device context holds (contiguous in
    global candidate order); also what a one-process-per-GPU caller uploads per rank.

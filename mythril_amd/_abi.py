@@ -50,6 +50,29 @@ class MqModelBatch(C.Structure):
     ]
 
 
+class MqRowPatch(C.Structure):
+    _fields_ = [("row", C.c_uint32), ("keep", C.c_uint32), ("bits", C.c_uint32)]
+
+
+class MqRowFloor(C.Structure):
+    _fields_ = [("row0", C.c_uint32), ("n_limbs", C.c_uint32), ("minimum", C.c_uint32)]
+
+
+class MqDerivation(C.Structure):
+    _fields_ = [
+        ("n_base", C.c_int64),
+        ("base_words", C.POINTER(C.c_uint32)),
+        ("n_derived", C.c_int64),
+        ("src", C.POINTER(C.c_int32)),
+        ("n_blocks", C.c_int32),
+        ("block_start", C.POINTER(C.c_int64)),
+        ("patch_ptr", C.POINTER(C.c_int64)),
+        ("patches", C.POINTER(MqRowPatch)),
+        ("floor_ptr", C.POINTER(C.c_int64)),
+        ("floors", C.POINTER(MqRowFloor)),
+    ]
+
+
 class MqStats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_double),
@@ -89,7 +112,8 @@ def as_model_batch(mb: ModelBatch):
     vw = np.ascontiguousarray(mb.var_widths, dtype=np.uint16)
     if vw.size == 0:
         vw = np.zeros(1, np.uint16)
-    words = np.ascontiguousarray(mb.var_words, dtype=np.uint32)
+    # (a derived batch carries no rows: mq_models_upload_derived ignores var_words)
+    words = np.ascontiguousarray(mb.var_words, dtype=np.uint32) if mb.var_words is not None else np.zeros(1, np.uint32)
     if words.size == 0:
         words = np.zeros(1, np.uint32)
     funcs = np.ascontiguousarray(mb.func_arr)
@@ -99,10 +123,29 @@ def as_model_batch(mb: ModelBatch):
     elb = np.ascontiguousarray(mb.else_base, dtype=np.int64)
     elw = np.ascontiguousarray(mb.else_words, dtype=np.uint32)
     s = MqModelBatch(
-        mb.n_models, mb.index_base, mb.n_vars, _ptr(vw, C.c_uint16), _ptr(words, C.c_uint32),
+        mb.n_models, mb.index_base, mb.n_vars, _ptr(vw, C.c_uint16),
+        _ptr(words, C.c_uint32) if mb.var_words is not None else C.POINTER(C.c_uint32)(),
         len(mb.funcs), funcs.ctypes.data, _ptr(eptr, C.c_int64), _ptr(ebase, C.c_int64),
         _ptr(ew, C.c_uint32), ew.size, _ptr(elb, C.c_int64), _ptr(elw, C.c_uint32), elw.size)
     return s, (vw, words, funcs, eptr, ebase, ew, elb, elw)
+
+
+def as_derivation(d):
+    """``mq_derivation`` over the arrays of a :class:`mythril_amd.candidates.Derivation`."""
+    base = np.ascontiguousarray(d.base_words, dtype=np.uint32)
+    n_base = int(d.n_base)
+    src = np.ascontiguousarray(d.src, dtype=np.int32)
+    bs = np.ascontiguousarray(d.block_start, dtype=np.int64)
+    pp = np.ascontiguousarray(d.patch_ptr, dtype=np.int64)
+    fp = np.ascontiguousarray(d.floor_ptr, dtype=np.int64)
+    pa = np.ascontiguousarray(d.patches, dtype=np.uint32).reshape(-1, 3)
+    fl = np.ascontiguousarray(d.floors, dtype=np.uint32).reshape(-1, 3)
+
+    def ptr(a, ctype):
+        return C.cast(a.ctypes.data, C.POINTER(ctype)) if a.size else C.POINTER(ctype)()
+    s = MqDerivation(n_base, ptr(base, C.c_uint32), len(src), ptr(src, C.c_int32), len(bs) - 1,
+                     ptr(bs, C.c_int64), ptr(pp, C.c_int64), ptr(pa, MqRowPatch), ptr(fp, C.c_int64), ptr(fl, MqRowFloor))
+    return s, (base, src, bs, pp, fp, pa, fl)
 
 
 def as_dag_batch(db):

@@ -254,10 +254,127 @@ def _candidate_rows(lru: ModelBatch, src: np.ndarray, starts: np.ndarray, sizes:
     return np.concatenate([lru.var_words, gen], axis=1)
 
 
+class Derivation:
+    """The generated candidates' rows as "the LRU rows, patched" — the arrays of ``mq_derivation``
+    (include/mq.h): the device expands them (``Evaluator.upload_models_derived``), so the
+    ``[rows, n_lru + K]`` matrix is neither built on the host nor sent over the bus.
+
+    ``base_words`` [rows, n_base]; ``src`` int32[K] (-1: all-zero rows); ``block_start`` /
+    ``patch_ptr`` / ``floor_ptr`` int64[n_blocks + 1]; ``patches`` uint32[n, 3] of (row, keep, bits):
+    ``w = (w & keep) | bits``, at most one per (block, row); ``floors`` uint32[n, 3] of (row0,
+    n_limbs, minimum), applied after the block's patches."""
+
+    def __init__(self, base_words, src, block_start, patch_ptr, patches, floor_ptr, floors):
+        self.base_words = np.ascontiguousarray(base_words, np.uint32)
+        self.n_base = int(self.base_words.shape[1])
+        self.src = np.ascontiguousarray(src, np.int32)
+        self.block_start = np.ascontiguousarray(block_start, np.int64)
+        self.patch_ptr = np.ascontiguousarray(patch_ptr, np.int64)
+        self.patches = np.ascontiguousarray(patches, np.uint32).reshape(-1, 3)
+        self.floor_ptr = np.ascontiguousarray(floor_ptr, np.int64)
+        self.floors = np.ascontiguousarray(floors, np.uint32).reshape(-1, 3)
+
+    @property
+    def n_derived(self) -> int:
+        return len(self.src)
+
+    @property
+    def n_blocks(self) -> int:
+        return len(self.block_start) - 1
+
+    def upload_bytes(self) -> int:
+        """Host-to-device bytes of the variable rows' description."""
+        return 4 * self.base_words.size + 12 * len(self.patches) + 12 * len(self.floors) + 4 * len(self.src)
+
+
+def _compose_blocks(blocks: List[Tuple[Tuple, np.ndarray]], off: np.ndarray, syms):
+    """Per block: ({limb row: [mask, bits]} of its value assignments composed in patch order — the
+    last assignment of a bit wins — and {variable: minimum} of its floors).  The composition the
+    numpy form of :func:`_candidate_rows` does in ``row_ops`` / ``floor_ops``."""
+    cache: Dict[Tuple, List[Tuple[int, int, int]]] = {}
+    out = []
+    for patch, _ in blocks:
+        rows: Dict[int, List[int]] = {}
+        floors: Dict[int, int] = {}
+        for el in patch:
+            if el[1] < 0:   # size >= minimum (values < 2^32 in their low limb)
+                if floors.get(el[0], 0) < el[3]:
+                    floors[el[0]] = el[3]
+                continue
+            ups = cache.get(el)
+            if ups is None:
+                v, lo, n, bits = el
+                ups = []
+                o = int(off[v])
+                for i in range(lo // 32, (lo + n - 1) // 32 + 1):
+                    blo = 32 * i
+                    a, b2 = max(lo, blo), min(lo + n, blo + 32)
+                    mask = ((1 << (b2 - a)) - 1) << (a - blo)
+                    ups.append((o + i, mask, ((bits >> (a - lo)) << (a - blo)) & mask))
+                cache[el] = ups
+            for row, mask, val in ups:
+                c = rows.get(row)
+                if c is None:
+                    rows[row] = [mask, val]
+                else:
+                    c[1] = (c[1] & ~mask) | val
+                    c[0] |= mask
+        out.append((rows, floors))
+    return out
+
+
+def derivation_arrays(lru: ModelBatch, base: np.ndarray, blocks: List[Tuple[Tuple, np.ndarray]], starts: np.ndarray,
+                      sizes: np.ndarray, off: np.ndarray, syms, composed=None) -> Derivation:
+    """``(blocks, starts, sizes, off, syms)`` as a :class:`Derivation` over the LRU batch ``lru``:
+    each block's value assignments composed per limb row into one ``(keep, bits)``, its floors as
+    ``(row0, n_limbs, minimum)``.  ``base`` is the LRU index of every candidate (-1: none)."""
+    if composed is None:
+        composed = _compose_blocks(blocks, off, syms)
+    widths = syms.var_widths
+    pptr = np.zeros(len(blocks) + 1, np.int64)
+    fptr = np.zeros(len(blocks) + 1, np.int64)
+    patches: List[Tuple[int, int, int]] = []
+    floors: List[Tuple[int, int, int]] = []
+    for j, (rows, fl) in enumerate(composed):
+        for row in sorted(rows):
+            mask, val = rows[row]
+            patches.append((row, ~mask & 0xFFFFFFFF, val))
+        for v in sorted(fl):
+            floors.append((int(off[v]), limbs(widths[v]), fl[v]))
+        pptr[j + 1] = len(patches)
+        fptr[j + 1] = len(floors)
+    src = np.asarray(base, np.int64) if lru.n_models else np.full(len(base), -1, np.int64)
+    return Derivation(lru.var_words, src, np.asarray(starts, np.int64), pptr,
+                      np.asarray(patches, np.uint64).reshape(-1, 3), fptr, np.asarray(floors, np.uint64).reshape(-1, 3))
+
+
 class CandidateSet:
     """The LRU models followed by the generated candidates, serialized (``batch``), plus what is
     needed to turn a generated candidate back into a model (:meth:`materialize`).  Candidates
-    come in blocks: one patch applied to a range of base models."""
+    come in blocks: one patch applied to a range of base models.
+
+    From a generator with ``device_rows`` the set carries a :class:`Derivation` instead of the
+    variable rows: ``batch.var_words`` is absent (the device expands the rows), and :meth:`rows`
+    materialises the matrix on demand."""
+
+    derivation: Optional[Derivation] = None
+    _row_args = None
+
+    def rows(self) -> np.ndarray:
+        """The whole batch's variable rows [rows, n_lru + K] (:func:`_candidate_rows`; as
+        uploaded, before the device masks them to the variables' widths)."""
+        if self.batch.var_words is not None:
+            return self.batch.var_words
+        lru, src, starts, sizes, blocks, off, K = self._row_args
+        return _candidate_rows(lru, src, starts, sizes, blocks, self.syms, off, K)
+
+    def host_batch(self) -> ModelBatch:
+        """``batch`` with its variable rows on the host (oracle re-checks)."""
+        b = self.batch
+        if b.var_words is not None:
+            return b
+        return ModelBatch(b.var_widths, self.rows(), b.funcs, b.entry_ptr, b.entry_words, b.entry_base,
+                          b.else_words, b.else_base, b.index_base)
 
     def __init__(self, batch: ModelBatch, n_lru: int, base: np.ndarray, block_of: np.ndarray,
                  block_patches: List[Tuple], syms, lru_models):
@@ -317,8 +434,11 @@ class CandidateGenerator:
     """Generates up to ``max_candidates`` candidates for a batch of conjunctions (seeded)."""
 
     def __init__(self, max_candidates: int = 100_000, seed: int = 0, random_frac: float = 0.05, per_query: int = 16,
-                 fill: bool = False):
+                 fill: bool = False, device_rows: bool = False):
         self.max_candidates = int(max_candidates)
+        # the candidates' variable rows are not materialised: the set carries a Derivation for
+        # Evaluator.upload_models_derived (VerdictEngine.candidate_first_hits, one device)
+        self.device_rows = bool(device_rows)
         self.rng = np.random.Generator(np.random.PCG64(seed))
         self.random_frac = random_frac
         self.per_query = int(per_query)   # patches per query (each over every base model)
@@ -453,11 +573,25 @@ class CandidateGenerator:
         starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         off = lru.var_word_offsets()
         src = np.where(base >= 0, base, 0)
-        words = _candidate_rows(lru, src, starts, sizes, blocks, syms, off, K)
         M = n_lru + K
+        composed = deriv = None
+        if self.device_rows:
+            # the rows stay a description (Derivation) the device expands; only the patched derived
+            # variables' values, which enter the function tables below, are computed here
+            composed = _compose_blocks(blocks, off, syms)
+            deriv = derivation_arrays(lru, base, blocks, starts, sizes, off, syms, composed)
+            words = None
+        else:
+            words = _candidate_rows(lru, src, starts, sizes, blocks, syms, off, K)
+
+        def done(mb: ModelBatch) -> CandidateSet:
+            cs = CandidateSet(mb, n_lru, base, block_of, [p for p, _ in blocks], syms, lru_models)
+            if deriv is not None:
+                cs.derivation = deriv
+                cs._row_args = (lru, src, starts, sizes, blocks, off, K)
+            return cs
         if not lru.funcs:
-            return CandidateSet(ModelBatch(lru.var_widths, words), n_lru, base, block_of,
-                                [p for p, _ in blocks], syms, lru_models)
+            return done(ModelBatch(lru.var_widths, words, n_models=M))
         # function tables: the base model's entries, preceded by an entry for every derived variable
         # of that function the candidate's patch changed (so table and derived column agree; first
         # match wins)
@@ -515,7 +649,31 @@ class CandidateGenerator:
                 nl = limbs(syms.var_widths[int(uv[0])])
                 out[rows, :klen] = keys[vinv[rep]]
                 vrow = off[uv][vinv[rep]]
-                out[rows, klen:klen + nl] = words[vrow[:, None] + np.arange(nl)[None, :], (n_lru + cols)[:, None]]
+                if words is not None:
+                    out[rows, klen:klen + nl] = words[vrow[:, None] + np.arange(nl)[None, :], (n_lru + cols)[:, None]]
+                else:
+                    # the same values without the matrix: the base model's limbs of that variable
+                    # under the block's composed (keep, bits), then its floor
+                    keep_t = np.full((len(tj), nl), 0xFFFFFFFF, np.uint32)
+                    bits_t = np.zeros((len(tj), nl), np.uint32)
+                    mins_t = np.zeros(len(tj), np.uint32)
+                    for t, (j, v) in enumerate(zip(trip[0], trip[2])):
+                        prow, pfl = composed[j]
+                        for i in range(nl):
+                            c = prow.get(int(off[v]) + i)
+                            if c is not None:
+                                keep_t[t, i], bits_t[t, i] = ~c[0] & 0xFFFFFFFF, c[1]
+                        mins_t[t] = pfl.get(v, 0)
+                    if n_lru:
+                        vals = lru.var_words[vrow[:, None] + np.arange(nl)[None, :], src[cols][:, None]]
+                    else:
+                        vals = np.zeros((len(cols), nl), np.uint32)
+                    vals = (vals & keep_t[rep]) | bits_t[rep]
+                    mn = mins_t[rep]
+                    if mn.any():
+                        small = ~vals[:, 1:].any(axis=1)
+                        vals[:, 0] = np.where(small & (vals[:, 0] < mn), mn, vals[:, 0])
+                    out[rows, klen:klen + nl] = vals
             if n_lru and K:
                 gstart = gstarts + add_cnt
                 rep = cnt_gen
@@ -537,6 +695,5 @@ class CandidateGenerator:
             el = np.concatenate([lel, gel]).reshape(-1)
             el_chunks.append(el)
             epos += el.size
-        mb = ModelBatch(lru.var_widths, words, lru.funcs, eptr, np.concatenate(ew_chunks), ebase,
-                        np.concatenate(el_chunks), elb, 0)
-        return CandidateSet(mb, n_lru, base, block_of, [p for p, _ in blocks], syms, lru_models)
+        return done(ModelBatch(lru.var_widths, words, lru.funcs, eptr, np.concatenate(ew_chunks), ebase,
+                               np.concatenate(el_chunks), elb, 0, n_models=M))

@@ -370,6 +370,8 @@ struct mq_ctx {
   DevBuf kec_data, kec_off, kec_out;   // mq_keccak256 buffers, grown and kept across calls
   DevBuf rowmask;   // per-row masks applied to uploaded variable words
   DevBuf mpack;     // UploadPack block of the model batch's small tables (upload_one: the views above point in)
+  // a derived upload's base rows and derivation tables (views into mpack, read by launch_derive_rows)
+  DevBuf dv_base, dv_src, dv_bstart, dv_pptr, dv_patches, dv_fptr, dv_floors;
   // Bool variables as packed lane masks [tile][n_bmask] (G kernel PUSH_PKB): bmask_of_var[v] =
   // mask index of Bool variable v (-1: none); bmask_rows[j] = its variable row
   std::vector<int32_t> bmask_of_var;
@@ -993,7 +995,9 @@ void mq_ctx_destroy(mq_ctx* c) {
 }
 
 // Upload a model batch to ONE device (n_models may be 0: an empty shard evaluates to "no hit").
-static int upload_one(mq_ctx* c, const mq_model_batch* mb) {
+// dv (mq_models_upload_derived, checked by mq_derivation_check): the variable rows are not
+// mb->var_words but dv's base rows and tables, expanded on the device; everything else is shared.
+static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* dv = nullptr) {
   if (!c || !mb || mb->n_models < 0 || mb->n_vars < 0 || mb->n_funcs < 0) return MQ_ERR_ARG;
   if (mb->n_models > 0x7FFFFFFF || mb->index_base + mb->n_models > 0x7FFFFFFE) return MQ_ERR_ARG;
   HIPCHK(hipSetDevice(c->device));
@@ -1005,7 +1009,7 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb) {
     vnl[v] = (uint32_t)nl_of(mb->var_width[v]);
     rows += vnl[v];
   }
-  if (rows > 0 && !mb->var_words) return MQ_ERR_ARG;
+  if (rows > 0 && !dv && !mb->var_words) return MQ_ERR_ARG;
   // functions: SoA else block, CSR entries copied as is
   const int F = mb->n_funcs;
   std::vector<FuncDev> fd(std::max(F, 1));
@@ -1072,7 +1076,22 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb) {
   UploadPack pk;
   // variable rows followed by one all-zero row (the QSA preload points absent limbs at it)
   HIPCHK(c->vars.ensure(sizeof(uint32_t) * (size_t)(rows + 1) * M));
-  {
+  for (DevBuf* b : {&c->dv_base, &c->dv_src, &c->dv_bstart, &c->dv_pptr, &c->dv_patches, &c->dv_fptr, &c->dv_floors})
+    b->release();   // (views of the previous derived upload's block)
+  if (dv) {
+    // the base rows and the derivation tables ride in the staged block; the rows themselves are
+    // written by launch_derive_rows below, once the block is on the device
+    const size_t nb = (size_t)dv->n_blocks;
+    const int64_t z2[2] = {0, 0};
+    pk.add(c->dv_base, dv->base_words, (size_t)rows * (size_t)dv->n_base, 1);
+    pk.add(c->dv_src, dv->src, (size_t)dv->n_derived, 1);
+    pk.add(c->dv_bstart, nb ? dv->block_start : z2, nb + 1);
+    pk.add(c->dv_pptr, nb ? dv->patch_ptr : z2, nb + 1);
+    pk.add(c->dv_patches, dv->patches, nb ? (size_t)dv->patch_ptr[nb] : 0, 1);
+    pk.add(c->dv_fptr, nb ? dv->floor_ptr : z2, nb + 1);
+    pk.add(c->dv_floors, dv->floors, nb ? (size_t)dv->floor_ptr[nb] : 0, 1);
+    HIPCHK(hipMemsetAsync((uint32_t*)c->vars.p + (size_t)rows * M, 0, sizeof(uint32_t) * (size_t)M, c->stream));
+  } else {
     const size_t n = sizeof(uint32_t) * (size_t)rows * M, nz = sizeof(uint32_t) * (size_t)M;
     if (n + nz <= StageRing::kMaxStaged) {
       // (a drop-in batch's rows are a few KB: the rows and the zero row in one staged copy, no sync)
@@ -1173,6 +1192,12 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb) {
   pk.add(c->else_words, else_soa.data(), else_soa.size());
   pk.add(c->dense_words, dense.data(), dense.size());
   HIPCHK(pk.commit(c->mpack, c->stream, c->stage));
+  if (dv)
+    HIPCHK(launch_derive_rows(c->vars.as<uint32_t>(), c->dv_base.as<uint32_t>(), c->dv_src.as<int32_t>(),
+                              c->dv_bstart.as<int64_t>(), c->dv_pptr.as<int64_t>(), c->dv_patches.as<RowPatch>(),
+                              c->dv_fptr.as<int64_t>(), c->dv_floors.as<RowFloor>(),
+                              dv->n_blocks ? dv->floor_ptr[dv->n_blocks] : 0, dv->n_base, dv->n_derived, rows,
+                              dv->n_blocks, c->stream));
   if (need_mask) HIPCHK(launch_mask_rows(c->vars.as<uint32_t>(), c->rowmask.as<uint32_t>(), rows, M, c->stream));
   HIPCHK(launch_pack_bool(c->vars.as<uint32_t>(), c->bmasks.as<uint64_t>(), c->bmask_rows.as<uint32_t>(), nullptr,
                           c->n_bmask, c->n_bmask, M, c->stream));
@@ -1241,21 +1266,79 @@ void mq_models_shard_free(void* handle) { delete static_cast<ShardBuffers*>(hand
 
 static constexpr int64_t kWideMaxEntries = 64;
 
+// Per-batch bookkeeping every upload entry point does on all devices of the context.
+static void note_batch(mq_ctx* c, const mq_model_batch* mb) {
+  std::vector<int64_t> mx((size_t)std::max(mb->n_funcs, 0), 0);
+  if (mb->entry_ptr)
+    for (int f = 0; f < mb->n_funcs; f++) {
+      const int64_t* p = mb->entry_ptr + (int64_t)f * (mb->n_models + 1);
+      for (int64_t m = 0; m < mb->n_models; m++) mx[f] = std::max(mx[f], p[m + 1] - p[m]);
+    }
+  for (mq_ctx* d : devices_of(c)) {
+    d->func_max_entries = mx;
+    d->batch_gen++;
+  }
+}
+
+static_assert(sizeof(mq_row_patch) == sizeof(RowPatch) && sizeof(mq_row_floor) == sizeof(RowFloor) &&
+                  sizeof(mq_row_patch) == 12 && sizeof(mq_row_floor) == 12,
+              "the derivation tables go to the device as they are");
+
+int mq_derivation_check(const mq_model_batch* mb, const mq_derivation* d) {
+  if (!mb || !d || mb->n_models < 0 || mb->n_vars < 0 || (mb->n_vars > 0 && !mb->var_width)) return MQ_ERR_ARG;
+  if (d->n_base < 0 || d->n_derived < 0 || d->n_blocks < 0) return MQ_ERR_ARG;
+  if (d->n_base > 0x7FFFFFFF || d->n_derived > 0x7FFFFFFF || d->n_base + d->n_derived != mb->n_models) return MQ_ERR_ARG;
+  int64_t rows = 0;
+  for (int v = 0; v < mb->n_vars; v++) rows += nl_of(mb->var_width[v]);
+  if (rows > 0 && d->n_base > 0 && !d->base_words) return MQ_ERR_ARG;
+  const int64_t K = d->n_derived, nb = d->n_blocks;
+  if (K > 0 && (!d->src || nb < 1)) return MQ_ERR_ARG;
+  for (int64_t k = 0; k < K; k++)
+    if (d->src[k] < -1 || d->src[k] >= d->n_base) return MQ_ERR_ARG;
+  if (nb == 0) return MQ_OK;
+  if (!d->block_start || !d->patch_ptr || !d->floor_ptr) return MQ_ERR_ARG;
+  if (d->block_start[0] != 0 || d->block_start[nb] != K || d->patch_ptr[0] != 0 || d->floor_ptr[0] != 0) return MQ_ERR_ARG;
+  for (int64_t j = 0; j < nb; j++)
+    if (d->block_start[j + 1] < d->block_start[j] || d->patch_ptr[j + 1] < d->patch_ptr[j] ||
+        d->floor_ptr[j + 1] < d->floor_ptr[j])
+      return MQ_ERR_ARG;
+  const int64_t np = d->patch_ptr[nb], nf = d->floor_ptr[nb];
+  if ((np > 0 && !d->patches) || (nf > 0 && !d->floors)) return MQ_ERR_ARG;
+  for (int64_t p = 0; p < np; p++)
+    if ((int64_t)d->patches[p].row >= rows) return MQ_ERR_ARG;
+  for (int64_t f = 0; f < nf; f++)
+    if (d->floors[f].n_limbs < 1 || (int64_t)d->floors[f].row0 + (int64_t)d->floors[f].n_limbs > rows) return MQ_ERR_ARG;
+  return MQ_OK;
+}
+
+int mq_models_upload_derived(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* d) {
+  // (host checks first: a malformed call answers before any device call)
+  if (mq_derivation_check(mb, d) != MQ_OK) return MQ_ERR_ARG;
+  if (!c || !c->peers.empty()) return MQ_ERR_ARG;
+  PhaseTimer pt(&c->host_t[8]);
+  note_batch(c, mb);
+  c->shard_lo.assign(1, 0);
+  c->M_total = mb->n_models;
+  return upload_one(c, mb, d);
+}
+
+int mq_models_download_vars(mq_ctx* c, uint32_t* out, int64_t n_words) {
+  if (!c || !c->peers.empty() || n_words < 0 || (n_words > 0 && !out)) return MQ_ERR_ARG;
+  if (!c->have_models) return MQ_ERR_NO_MODELS;
+  int64_t rows = 0;
+  for (uint32_t nl : c->var_nl_h) rows += nl;
+  if (n_words != rows * c->M) return MQ_ERR_ARG;
+  if (n_words == 0) return MQ_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(out, c->vars.p, sizeof(uint32_t) * (size_t)n_words, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MQ_OK;
+}
+
 int mq_models_upload(mq_ctx* c, const mq_model_batch* mb) {
   if (!c || !mb || mb->n_models < 0) return MQ_ERR_ARG;
   PhaseTimer pt(&c->host_t[8]);
-  {
-    std::vector<int64_t> mx((size_t)std::max(mb->n_funcs, 0), 0);
-    if (mb->entry_ptr)
-      for (int f = 0; f < mb->n_funcs; f++) {
-        const int64_t* p = mb->entry_ptr + (int64_t)f * (mb->n_models + 1);
-        for (int64_t m = 0; m < mb->n_models; m++) mx[f] = std::max(mx[f], p[m + 1] - p[m]);
-      }
-    for (mq_ctx* d : devices_of(c)) {
-      d->func_max_entries = mx;
-      d->batch_gen++;
-    }
-  }
+  note_batch(c, mb);
   if (c->peers.empty()) {
     c->shard_lo.assign(1, 0);
     c->M_total = mb->n_models;

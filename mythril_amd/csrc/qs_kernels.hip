@@ -1040,6 +1040,99 @@ hipError_t launch_pack_bool(const uint32_t* vars, uint64_t* masks, const uint32_
   return hipGetLastError();
 }
 
+// Derived upload (qs_launch.h launch_derive_rows).  One thread owns one model column for a chunk
+// of kDeriveRowChunk rows (grid.y), so a wave's stores along the model axis are 256 contiguous
+// bytes per row.  The thread that copies a word is the one that patches it (a second store of
+// the patched base word: a block has at most one patch per row), so no ordering between threads
+// is needed.  Blocks are contiguous in k, hence a wave normally lies inside one block and walks
+// its patch list with wave-uniform indices; a wave that straddles a block boundary walks per lane.
+// The base matrix (<= 100 models in the product path) is left to L2.
+static constexpr int kDeriveRowChunk = 16;
+
+__device__ __forceinline__ int derive_block_of(const int64_t* block_start, int n_blocks, int64_t k) {
+  int lo = 0, hi = n_blocks;   // the last block whose start is <= k (empty blocks before it are skipped)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (block_start[mid] <= k) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void derive_rows_kernel(uint32_t* vars, const uint32_t* base, const int32_t* src,
+                                                          const int64_t* block_start, const int64_t* patch_ptr,
+                                                          const RowPatch* patches, int64_t n_base, int64_t K,
+                                                          int64_t rows, int n_blocks) {
+  const size_t M = (size_t)(n_base + K);
+  const size_t m = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const size_t r0 = (size_t)blockIdx.y * kDeriveRowChunk;
+  const size_t r1 = r0 + kDeriveRowChunk < (size_t)rows ? r0 + kDeriveRowChunk : (size_t)rows;
+  const bool derived = m >= (size_t)n_base;
+  const int64_t k = (int64_t)m - n_base;
+  const int64_t s = derived ? (int64_t)src[k] : (int64_t)m;
+  const uint32_t* col = base + (s >= 0 ? (size_t)s : 0);
+#pragma unroll 4
+  for (size_t r = r0; r < r1; r++) vars[r * M + m] = s >= 0 ? col[r * (size_t)n_base] : 0u;
+  if (!derived) return;
+  const int j = derive_block_of(block_start, n_blocks, k);
+  const int jf = __builtin_amdgcn_readfirstlane(j);
+  if (__all(j == jf)) {
+    const int64_t p1 = patch_ptr[jf + 1];
+    for (int64_t p = patch_ptr[jf]; p < p1; p++) {
+      const RowPatch q = patches[p];
+      if (q.row >= r0 && q.row < r1) {
+        const uint32_t w = s >= 0 ? col[(size_t)q.row * (size_t)n_base] : 0u;
+        vars[(size_t)q.row * M + m] = (w & q.keep) | q.bits;
+      }
+    }
+  } else {
+    const int64_t p1 = patch_ptr[j + 1];
+    for (int64_t p = patch_ptr[j]; p < p1; p++) {
+      const RowPatch q = patches[p];
+      if (q.row >= r0 && q.row < r1) {
+        const uint32_t w = s >= 0 ? col[(size_t)q.row * (size_t)n_base] : 0u;
+        vars[(size_t)q.row * M + m] = (w & q.keep) | q.bits;
+      }
+    }
+  }
+}
+
+// The floors of each derived model's block, after derive_rows_kernel on the same stream: one
+// thread per derived model (a floor reads every limb of its variable).
+__global__ __launch_bounds__(256) void derive_floors_kernel(uint32_t* vars, const int64_t* block_start,
+                                                            const int64_t* floor_ptr, const RowFloor* floors,
+                                                            int64_t n_base, int64_t K, int n_blocks) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= K) return;
+  const size_t M = (size_t)(n_base + K), m = (size_t)(n_base + k);
+  const int j = derive_block_of(block_start, n_blocks, k);
+  const int64_t f1 = floor_ptr[j + 1];
+  for (int64_t f = floor_ptr[j]; f < f1; f++) {
+    const RowFloor q = floors[f];
+    uint32_t high = 0;
+    for (uint32_t l = 1; l < q.n_limbs; l++) high |= vars[(size_t)(q.row0 + l) * M + m];
+    uint32_t* w0 = vars + (size_t)q.row0 * M + m;
+    if (high == 0 && *w0 < q.minimum) *w0 = q.minimum;
+  }
+}
+
+hipError_t launch_derive_rows(uint32_t* vars, const uint32_t* base, const int32_t* src, const int64_t* block_start,
+                              const int64_t* patch_ptr, const RowPatch* patches, const int64_t* floor_ptr,
+                              const RowFloor* floors, int64_t n_floors, int64_t n_base, int64_t K, int64_t rows,
+                              int32_t n_blocks, hipStream_t st) {
+  const int64_t M = n_base + K;
+  if (rows <= 0 || M <= 0) return hipSuccess;
+  const int64_t gy = (rows + kDeriveRowChunk - 1) / kDeriveRowChunk;
+  if (gy > 65535 || (K > 0 && n_blocks < 1)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(derive_rows_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)gy), dim3(256), 0, st, vars, base,
+                     src, block_start, patch_ptr, patches, n_base, K, rows, (int)n_blocks);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || n_floors <= 0 || K <= 0) return e;
+  hipLaunchKernelGGL(derive_floors_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, vars, block_start,
+                     floor_ptr, floors, n_base, K, (int)n_blocks);
+  return hipGetLastError();
+}
+
 __global__ void qs_init_best(int32_t* best, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) best[i] = 0x7FFFFFFF;

@@ -122,6 +122,21 @@ hipError_t launch_mask_rows(uint32_t* vars, const uint32_t* rowmask, int64_t row
 // (list == nullptr: j = 0..n-1)
 hipError_t launch_pack_bool(const uint32_t* vars, uint64_t* masks, const uint32_t* rows, const int32_t* list, int n,
                             int n_masks, int64_t M, hipStream_t st);
+// Derived upload (mq_models_upload_derived): the variable rows [rows, M = n_base + K] written on
+// the device.  Column m < n_base is base[row * n_base + m]; column n_base + k is the column of
+// src[k] (-1: zeros) with the patches of k's block (block_start: [n_blocks + 1], patch_ptr into
+// patches) applied, then (a second launch on the same stream, so a floor sees every patched limb
+// of its variable) the block's floors.  RowPatch / RowFloor are mq.h's mq_row_patch / mq_row_floor.
+struct RowPatch {
+  uint32_t row, keep, bits;
+};
+struct RowFloor {
+  uint32_t row0, n_limbs, minimum;
+};
+hipError_t launch_derive_rows(uint32_t* vars, const uint32_t* base, const int32_t* src, const int64_t* block_start,
+                              const int64_t* patch_ptr, const RowPatch* patches, const int64_t* floor_ptr,
+                              const RowFloor* floors, int64_t n_floors, int64_t n_base, int64_t K, int64_t rows,
+                              int32_t n_blocks, hipStream_t st);
 hipError_t launch_finalize_best(int32_t* best, const uint8_t* unsupported, int n, hipStream_t st);
 hipError_t launch_keccak(const uint8_t* data, const int64_t* offsets, int n, uint8_t* out, hipStream_t st);
 

@@ -15,7 +15,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ._abi import MqDagBatch, MqModelBatch, MqNode, MqStats, MqTapeBatch, as_dag_batch, as_model_batch, as_tape_batch
+from ._abi import (MqDagBatch, MqDerivation, MqModelBatch, MqNode, MqStats, MqTapeBatch, as_dag_batch, as_derivation,
+                   as_model_batch, as_tape_batch)
 from .models import ModelBatch
 from .tape import TapeBatch
 
@@ -92,6 +93,9 @@ def load_library(path: str = LIB_PATH):
         L.mq_models_shard.argtypes = [C.POINTER(MqModelBatch), C.c_int64, C.c_int64, C.POINTER(MqModelBatch), C.POINTER(P)]
         L.mq_models_shard_free.argtypes = [P]
         L.mq_models_shard_free.restype = None
+        L.mq_derivation_check.argtypes = [C.POINTER(MqModelBatch), C.POINTER(MqDerivation)]
+        L.mq_models_upload_derived.argtypes = [P, C.POINTER(MqModelBatch), C.POINTER(MqDerivation)]
+        L.mq_models_download_vars.argtypes = [P, C.POINTER(C.c_uint32), C.c_int64]
         _lib = L
         return L
 
@@ -413,6 +417,32 @@ class Evaluator:
         _check(self.lib.mq_models_upload(self.ctx, C.byref(s)), "mq_models_upload")
         self.n_models = mb.n_models
         self.index_base = mb.index_base
+        self._var_widths = mb.var_widths
+
+    def upload_models_derived(self, mb: ModelBatch, derivation) -> None:
+        """Replace the candidate set with ``derivation``'s base models followed by its derived
+        ones, their variable rows expanded on the device (``mq_models_upload_derived``).  ``mb``
+        describes all of them as for :meth:`upload_models`; its ``var_words`` may be absent.
+        Single-device evaluators only."""
+        s, keep = as_model_batch(mb)
+        d, keep_d = as_derivation(derivation)
+        self.upload_seq += 1
+        _check(self.lib.mq_models_upload_derived(self.ctx, C.byref(s), C.byref(d)), "mq_models_upload_derived")
+        self.n_models = mb.n_models
+        self.index_base = mb.index_base
+        self._var_widths = mb.var_widths
+
+    def download_vars(self) -> np.ndarray:
+        """Diagnostic: the resident variable rows ``uint32[rows, M]`` as the kernels read them
+        (masked to the variables' widths).  Single-device evaluators only."""
+        widths = getattr(self, "_var_widths", None)
+        if widths is None:
+            raise EvaluatorError("download_vars before an upload")
+        rows = int(np.maximum((widths.astype(np.int64) + 31) // 32, 1).sum())
+        out = np.zeros((rows, self.n_models), np.uint32)
+        _check(self.lib.mq_models_download_vars(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size),
+               "mq_models_download_vars")
+        return out
 
     # ------------------------------------------------------------ tapes
     def compile(self, tb: TapeBatch) -> CompiledTapes:

@@ -41,14 +41,22 @@ class ModelBatch:
                  funcs: Sequence[FuncSpec] = (), entry_ptr: Optional[np.ndarray] = None,
                  entry_words: Optional[np.ndarray] = None, entry_base: Optional[np.ndarray] = None,
                  else_words: Optional[np.ndarray] = None, else_base: Optional[np.ndarray] = None,
-                 index_base: int = 0):
+                 index_base: int = 0, n_models: Optional[int] = None):
         self.var_widths = np.asarray(var_widths, dtype=np.uint16)
-        self.var_words = np.ascontiguousarray(var_words, dtype=np.uint32)
         # limbs(w) per variable (Bool -> 1), vectorised: the drop-in path builds a batch per launch
         n_rows = int(np.maximum((self.var_widths.astype(np.int64) + 31) // 32, 1).sum())
-        if self.var_words.ndim != 2 or self.var_words.shape[0] != n_rows:
-            raise ValueError(f"var_words must be [{n_rows}, M], got {self.var_words.shape}")
-        self.n_models = int(self.var_words.shape[1])
+        if var_words is None:
+            # a derived batch (candidates.Derivation): its ``n_models`` rows are expanded on the
+            # device (Evaluator.upload_models_derived), the host holds the function tables only
+            if n_models is None:
+                raise ValueError("a batch without var_words needs n_models")
+            self.var_words = None
+            self.n_models = int(n_models)
+        else:
+            self.var_words = np.ascontiguousarray(var_words, dtype=np.uint32)
+            if self.var_words.ndim != 2 or self.var_words.shape[0] != n_rows:
+                raise ValueError(f"var_words must be [{n_rows}, M], got {self.var_words.shape}")
+            self.n_models = int(self.var_words.shape[1])
         self.funcs = list(funcs)
         F, M = len(self.funcs), self.n_models
         self.func_arr = np.zeros(max(F, 1), dtype=FUNC_DTYPE)

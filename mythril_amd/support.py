@@ -439,7 +439,15 @@ class VerdictEngine:
         t1 = clock()
         cs = generator.generate(db, inc.syms, inc.serialize(models), models)
         t2 = clock()
-        fh, t3, t4 = self._first_hit(db, cs.batch)
+        if cs.derivation is None:
+            fh, t3, t4 = self._first_hit(db, cs.batch)
+        elif len(getattr(self.evaluator, "devices", (0,))) == 1:
+            # generator.device_rows: the device expands the candidates' rows from the LRU's
+            fh, t3, t4 = self._first_hit(db, cs.batch, cs.derivation)
+        else:
+            mb = cs.host_batch()   # (a multi-device context shards host rows)
+            t2 = clock()
+            fh, t3, t4 = self._first_hit(db, mb)
         self.timing["lower"] += t1 - t0
         self.timing["serialize"] += t2 - t1
         self.timing["upload"] += t3 - t2
@@ -450,12 +458,15 @@ class VerdictEngine:
         fh = np.where(ok, fh, -2)
         return fh, cs
 
-    def _first_hit(self, tb, mb):
+    def _first_hit(self, tb, mb, derivation=None):
         """Upload + compile + first-hit launch; returns (first hits, time after upload, time
         after compile)."""
         clock = time.perf_counter
         ev = self.evaluator
-        ev.upload_models(mb)
+        if derivation is not None:
+            ev.upload_models_derived(mb, derivation)
+        else:
+            ev.upload_models(mb)
         t3 = clock()
         ct = ev.compile(tb)
         t4 = clock()
@@ -757,7 +768,9 @@ class ModelCache:
         if not todo:
             return out
         order = list(reversed(self.model_cache.lru_cache.keys()))
-        gen = CandidateGenerator(args.quick_sat_candidate_budget, seed=len(self.stats) + self.stats["queries"])
+        # MQ_DEVICE_CANDIDATES=1 (opt-in): the candidates' rows are derived on the device
+        gen = CandidateGenerator(args.quick_sat_candidate_budget, seed=len(self.stats) + self.stats["queries"],
+                                 device_rows=os.environ.get("MQ_DEVICE_CANDIDATES") == "1")
         fh, cs = self.engine.candidate_first_hits([exprs[i] for i in todo], order, gen)
         for i, h in zip(todo, fh):
             if h < 0:
