@@ -270,6 +270,62 @@ int mq_models_upload_derived(mq_ctx* ctx, const mq_model_batch* models, const mq
    upload. */
 int mq_models_download_vars(mq_ctx* ctx, uint32_t* out, int64_t n_words);
 
+/* Table derivation, passed alongside an mq_derivation: the function tables of the same
+   M = n_base + K models as "the base models' tables, plus a few entries per block", so the host
+   neither builds nor sends anything of size M for them.
+     base      the n_base base models' tables in the mq_model_batch layout: n_models == n_base,
+               n_funcs and funcs as the model description's; entry_ptr / entry_base / entry_words /
+               else_base / else_words are read, var_* are ignored.
+     add_ptr   [n_blocks + 1] into adds, the blocks being the row derivation's.
+     adds      one entry a block adds to a function: its value is, per derived model, that model's
+               resident (patched, floored, masked) limbs of variable `var`, its key the
+               limbs(arg0) (+ limbs(arg1)) constant words at key_words[key_off].
+   Resulting table of function f: model m < n_base has base model m's entries and else value;
+   derived model k of block j has one entry per addition of block j with func == f, in list
+   order (the generator lists them by ascending variable), then the entries of base model src[k]
+   in order (none, and else value 0, for src[k] == -1).  The first match wins, as in any table. */
+typedef struct mq_table_add { int32_t func, var; int64_t key_off; } mq_table_add;
+typedef struct mq_table_derivation {
+  const mq_model_batch* base;
+  const int64_t* add_ptr;
+  const mq_table_add* adds;
+  const uint32_t* key_words;
+  int64_t n_key_words;
+} mq_table_derivation;
+
+/* Host-only: MQ_OK when `d` is a well-formed derivation of `models` (mq_derivation_check; only
+   n_models, the widths, n_funcs and funcs of `models` are read) and `t` a well-formed table
+   derivation over it: add_ptr monotone from 0; every addition's func < n_funcs, var < n_vars,
+   limbs(width of var) == limbs(result width of func), key words inside the pool; at most one
+   addition per (block, func, var); base->n_models == n_base, base->n_funcs == n_funcs, its
+   entry_ptr rows monotone and non-negative, its entries and else values inside n_entry_words /
+   n_else_words.  Else MQ_ERR_ARG. */
+int mq_table_derivation_check(const mq_model_batch* models, const mq_derivation* d, const mq_table_derivation* t);
+
+/* mq_models_upload_derived with the function tables derived on the device as well.  Of `models`
+   only n_models, the widths, n_funcs, funcs and index_base are read: every per-model array may be
+   NULL.  Both host checks run before the device is touched (MQ_ERR_ARG leaves the resident models
+   as they were); afterwards the context is indistinguishable from mq_models_upload of the fully
+   materialised batch whose entry_base / else_base pack the functions in order.  Single-device
+   contexts only. */
+int mq_models_upload_derived_tables(mq_ctx* ctx, const mq_model_batch* models, const mq_derivation* d,
+                                    const mq_table_derivation* t);
+
+/* Diagnostic: the resident function tables.  mq_models_funcs_sizes fills sizes[4] = { words of
+   entry_ptr (n_funcs * (M + 1)), entry words INCLUDING the zero padding the table scan may read
+   past the last entry, else words, dense-slot words }.  mq_models_download_funcs copies them out,
+   the else values in the host (AoS) layout of mq_model_batch with the functions packed in order;
+   the dense slots as resident; info gets 5 values per function: { entry_base, dense_e (0: not
+   dense), dense_base, the largest per-model entry count, SoA else base }.  Any output may be NULL
+   (skipped); the counts must be those of mq_models_funcs_sizes.  Single-device contexts only. */
+int mq_models_funcs_sizes(mq_ctx* ctx, int64_t sizes[4]);
+int mq_models_download_funcs(mq_ctx* ctx, int64_t* entry_ptr, uint32_t* entry_words, uint32_t* else_words,
+                             uint32_t* dense_words, int64_t* info, const int64_t sizes[4]);
+
+/* Threads of the workgroup that scans a function's entry counts on the derived-table path (a
+   thread owns ceil(M / threads) consecutive models): tests size their boundary cases from it. */
+int mq_table_scan_threads(void);
+
 /* Host-only (no device needed): candidates [lo, hi) of `models` as a batch of their own, with
    index_base + lo — exactly the shard device g of a multi-device context holds (contiguous in
    global candidate order); also what a one-process-per-GPU caller uploads per rank.

@@ -73,6 +73,20 @@ class MqDerivation(C.Structure):
     ]
 
 
+class MqTableAdd(C.Structure):
+    _fields_ = [("func", C.c_int32), ("var", C.c_int32), ("key_off", C.c_int64)]
+
+
+class MqTableDerivation(C.Structure):
+    _fields_ = [
+        ("base", C.POINTER(MqModelBatch)),
+        ("add_ptr", C.POINTER(C.c_int64)),
+        ("adds", C.POINTER(MqTableAdd)),
+        ("key_words", C.POINTER(C.c_uint32)),
+        ("n_key_words", C.c_int64),
+    ]
+
+
 class MqStats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_double),
@@ -117,6 +131,13 @@ def as_model_batch(mb: ModelBatch):
     if words.size == 0:
         words = np.zeros(1, np.uint32)
     funcs = np.ascontiguousarray(mb.func_arr)
+    if mb.entry_ptr is None:
+        # (a batch whose tables are derived too: mq_models_upload_derived_tables reads the widths,
+        # the function signatures and index_base only)
+        null32, null64 = C.POINTER(C.c_uint32)(), C.POINTER(C.c_int64)()
+        s = MqModelBatch(mb.n_models, mb.index_base, mb.n_vars, _ptr(vw, C.c_uint16), null32, len(mb.funcs),
+                         funcs.ctypes.data, null64, null64, null32, 0, null64, null32, 0)
+        return s, (vw, funcs)
     eptr = np.ascontiguousarray(mb.entry_ptr, dtype=np.int64)
     ebase = np.ascontiguousarray(mb.entry_base, dtype=np.int64)
     ew = np.ascontiguousarray(mb.entry_words, dtype=np.uint32)
@@ -146,6 +167,20 @@ def as_derivation(d):
     s = MqDerivation(n_base, ptr(base, C.c_uint32), len(src), ptr(src, C.c_int32), len(bs) - 1,
                      ptr(bs, C.c_int64), ptr(pp, C.c_int64), ptr(pa, MqRowPatch), ptr(fp, C.c_int64), ptr(fl, MqRowFloor))
     return s, (base, src, bs, pp, fp, pa, fl)
+
+
+def as_table_derivation(t):
+    """``mq_table_derivation`` over a :class:`mythril_amd.candidates.TableDerivation`."""
+    base, keep_b = as_model_batch(t.base)
+    ap = np.ascontiguousarray(t.add_ptr, dtype=np.int64)
+    adds = np.zeros(len(t.add_func), dtype=np.dtype([("func", "<i4"), ("var", "<i4"), ("key_off", "<i8")]))
+    adds["func"], adds["var"], adds["key_off"] = t.add_func, t.add_var, t.add_key_off
+    keys = np.ascontiguousarray(t.key_words, dtype=np.uint32)
+
+    def ptr(a, ctype):
+        return C.cast(a.ctypes.data, C.POINTER(ctype)) if a.size else C.POINTER(ctype)()
+    s = MqTableDerivation(C.pointer(base), ptr(ap, C.c_int64), ptr(adds, MqTableAdd), ptr(keys, C.c_uint32), keys.size)
+    return s, (base, keep_b, ap, adds, keys)
 
 
 def as_dag_batch(db):

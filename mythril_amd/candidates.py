@@ -348,6 +348,174 @@ def derivation_arrays(lru: ModelBatch, base: np.ndarray, blocks: List[Tuple[Tupl
                       np.asarray(patches, np.uint64).reshape(-1, 3), fptr, np.asarray(floors, np.uint64).reshape(-1, 3))
 
 
+class TableDerivation:
+    """The generated candidates' function tables as "the LRU's tables, plus a few entries per
+    block" — the arrays of ``mq_table_derivation`` (include/mq.h), expanded on the device next to a
+    :class:`Derivation` (``Evaluator.upload_models_derived(..., tables=)``), so no table of
+    ``n_lru + K`` models is built on the host or sent over the bus.
+
+    ``base``: the LRU batch (its function CSR and else values are read); ``add_ptr``
+    int64[n_blocks + 1] into the additions; per addition ``add_func``, ``add_var`` (the entry's
+    value is the candidate's own limbs of that variable) and ``add_key_off`` into ``key_words``,
+    the constant key words.  A block's additions are listed per function by ascending variable,
+    which is their order in the resulting table, in front of the base model's entries."""
+
+    def __init__(self, base: ModelBatch, add_ptr, add_func, add_var, add_key_off, key_words):
+        self.base = base
+        self.add_ptr = np.ascontiguousarray(add_ptr, np.int64)
+        self.add_func = np.ascontiguousarray(add_func, np.int32)
+        self.add_var = np.ascontiguousarray(add_var, np.int32)
+        self.add_key_off = np.ascontiguousarray(add_key_off, np.int64)
+        self.key_words = np.ascontiguousarray(key_words, np.uint32)
+
+    @property
+    def n_blocks(self) -> int:
+        return len(self.add_ptr) - 1
+
+    def upload_bytes(self) -> int:
+        """Host-to-device bytes of the function tables' description."""
+        b = self.base
+        return (8 * b.entry_ptr.size + 4 * b.entry_words.size + 4 * b.else_words.size + 8 * self.add_ptr.size
+                + 16 * len(self.add_func) + 4 * self.key_words.size)
+
+
+def table_derivation_arrays(lru: ModelBatch, n_blocks: int, per_f, syms) -> TableDerivation:
+    """The triples of :func:`_table_triples` as a :class:`TableDerivation` over the LRU batch:
+    per block its additions ordered by (function, variable), each derived variable's constant
+    arguments once in the key pool."""
+    adds = sorted((j, f, v) for f, (tj, _, tv) in per_f.items() for j, v in zip(tj, tv))
+    key_off: Dict[int, int] = {}
+    keys: List[int] = []
+    for _, f, v in adds:
+        if v not in key_off:
+            key_off[v] = len(keys)
+            for aw, av in zip(lru.funcs[f].arg_widths, syms.derived[v][1]):
+                keys.extend(to_words(int(av), aw))
+    ptr = np.zeros(n_blocks + 1, np.int64)
+    if adds:
+        ptr[1:] = np.cumsum(np.bincount([j for j, _, _ in adds], minlength=n_blocks))
+    return TableDerivation(lru, ptr, [f for _, f, _ in adds], [v for _, _, v in adds],
+                           [key_off[v] for _, _, v in adds], np.asarray(keys, np.uint32))
+
+
+def _table_triples(lru: ModelBatch, blocks: List[Tuple[Tuple, np.ndarray]], syms):
+    """Per function: (block, position among the block's changed derived vars of it, var) triples:
+    the entries a block's patch adds in front of the base model's (per function by ascending
+    variable index)."""
+    func_index = {name: f for f, name in enumerate(syms.func_names)}
+    dfunc = {v: func_index[fn] for v, (fn, _) in syms.derived.items() if fn in func_index}
+    per_f: Dict[int, Tuple[List[int], List[int], List[int]]] = {}
+    for j, (patch, _) in enumerate(blocks):
+        vs = {el[0] for el in patch if el[0] in dfunc and el[1] >= 0}
+        if not vs:
+            continue
+        pos: Dict[int, int] = {}
+        for v in sorted(vs):
+            f = dfunc[v]
+            t = per_f.setdefault(f, ([], [], []))
+            t[0].append(j)
+            t[1].append(pos.get(f, 0))
+            t[2].append(v)
+            pos[f] = pos.get(f, 0) + 1
+    return per_f
+
+
+def _function_tables(lru: ModelBatch, blocks, syms, per_f, src, starts, sizes, off, K, words, composed):
+    """The fully materialised function tables of the LRU models followed by the K candidates:
+    ``(entry_ptr, entry_words, entry_base, else_words, else_base)``.  A candidate's table is its
+    base model's entries, preceded by an entry for every derived variable of that function its
+    block's patch changed (so table and derived column agree; first match wins).  ``words`` is the
+    batch's row matrix, or None with ``composed`` (:func:`_compose_blocks`) to compute the added
+    values from the LRU rows and the blocks' composed patches."""
+    n_lru = lru.n_models
+    M = n_lru + K
+    F = len(lru.funcs)
+    eptr = np.zeros((F, M + 1), np.int64)
+    ew_chunks, el_chunks = [], []
+    ebase = np.zeros(F, np.int64)
+    elb = np.zeros(F, np.int64)
+    wpos = epos = 0
+    for f, spec in enumerate(lru.funcs):
+        s = spec.stride
+        base_ptr = lru.entry_ptr[f]
+        base_cnt = np.diff(base_ptr)                                   # [n_lru]
+        cnt_gen = base_cnt[src] if n_lru else np.zeros(K, np.int64)
+        trip = per_f.get(f)
+        if trip is not None:
+            tj, ti, tv = (np.asarray(x, np.int64) for x in trip)
+            add_cnt = np.repeat(np.bincount(tj, minlength=len(blocks)), sizes)
+        else:
+            add_cnt = np.zeros(K, np.int64)
+        counts = np.concatenate([base_cnt, cnt_gen + add_cnt])
+        eptr[f, 1:] = np.cumsum(counts)
+        ent = lru.entry_words[int(lru.entry_base[f]):int(lru.entry_base[f]) + int(base_ptr[-1]) * s].reshape(-1, s)
+        out = np.zeros((int(eptr[f, -1]), s), np.uint32)
+        out[:int(base_ptr[-1])] = ent
+        gstarts = eptr[f, n_lru:n_lru + K]
+        if trip is not None:
+            # the changed derived vars' entries (key = their constant arguments, value = the
+            # candidate's patched column), one row per (triple, candidate of its block)
+            lens = sizes[tj]
+            rep = np.repeat(np.arange(len(tj)), lens)
+            within = np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
+            cols = starts[tj][rep] + within
+            rows = gstarts[cols] + ti[rep]
+            uv, vinv = np.unique(tv, return_inverse=True)
+            keys = np.asarray([[w for aw, av in zip(spec.arg_widths, syms.derived[int(v)][1])
+                                for w in to_words(int(av), aw)] for v in uv], np.uint32)
+            klen = keys.shape[1]
+            nl = limbs(syms.var_widths[int(uv[0])])
+            out[rows, :klen] = keys[vinv[rep]]
+            vrow = off[uv][vinv[rep]]
+            if words is not None:
+                out[rows, klen:klen + nl] = words[vrow[:, None] + np.arange(nl)[None, :], (n_lru + cols)[:, None]]
+            else:
+                # the same values without the matrix: the base model's limbs of that variable
+                # under the block's composed (keep, bits), then its floor
+                keep_t = np.full((len(tj), nl), 0xFFFFFFFF, np.uint32)
+                bits_t = np.zeros((len(tj), nl), np.uint32)
+                mins_t = np.zeros(len(tj), np.uint32)
+                for t, (j, v) in enumerate(zip(trip[0], trip[2])):
+                    prow, pfl = composed[j]
+                    for i in range(nl):
+                        c = prow.get(int(off[v]) + i)
+                        if c is not None:
+                            keep_t[t, i], bits_t[t, i] = ~c[0] & 0xFFFFFFFF, c[1]
+                    mins_t[t] = pfl.get(v, 0)
+                if n_lru:
+                    vals = lru.var_words[vrow[:, None] + np.arange(nl)[None, :], src[cols][:, None]]
+                else:
+                    vals = np.zeros((len(cols), nl), np.uint32)
+                vals = (vals & keep_t[rep]) | bits_t[rep]
+                mn = mins_t[rep]
+                if mn.any():
+                    small = ~vals[:, 1:].any(axis=1)
+                    vals[:, 0] = np.where(small & (vals[:, 0] < mn), mn, vals[:, 0])
+                out[rows, klen:klen + nl] = vals
+        if n_lru and K:
+            gstart = gstarts + add_cnt
+            rep = cnt_gen
+            tot = int(rep.sum())
+            if tot:
+                cand = np.repeat(np.arange(K), rep)
+                within = np.arange(tot) - np.repeat(np.cumsum(rep) - rep, rep)
+                dst = gstart[cand] + within
+                srcrow = base_ptr[src[cand]] + within
+                out[dst] = ent[srcrow]
+        ebase[f] = wpos
+        ew_chunks.append(out.reshape(-1))
+        wpos += out.size
+        nr = limbs(spec.result_width)
+        lel = lru.else_words[int(lru.else_base[f]):int(lru.else_base[f]) + n_lru * nr].reshape(-1, nr) \
+            if n_lru else np.zeros((0, nr), np.uint32)
+        gel = lel[src] if n_lru else np.zeros((K, nr), np.uint32)
+        elb[f] = epos
+        el = np.concatenate([lel, gel]).reshape(-1)
+        el_chunks.append(el)
+        epos += el.size
+    return eptr, np.concatenate(ew_chunks), ebase, np.concatenate(el_chunks), elb
+
+
 class CandidateSet:
     """The LRU models followed by the generated candidates, serialized (``batch``), plus what is
     needed to turn a generated candidate back into a model (:meth:`materialize`).  Candidates
@@ -358,6 +526,7 @@ class CandidateSet:
     materialises the matrix on demand."""
 
     derivation: Optional[Derivation] = None
+    table_derivation: Optional[TableDerivation] = None   # (a generator with ``device_tables``)
     _row_args = None
 
     def rows(self) -> np.ndarray:
@@ -373,6 +542,15 @@ class CandidateSet:
         b = self.batch
         if b.var_words is not None:
             return b
+        if b.entry_ptr is None:
+            # device_tables: the tables were not built either
+            lru, src, starts, sizes, blocks, off, K = self._row_args
+            words = self.rows()
+            if not lru.funcs:
+                return ModelBatch(b.var_widths, words)
+            per_f = _table_triples(lru, blocks, self.syms)
+            return ModelBatch(b.var_widths, words, b.funcs, *_function_tables(
+                lru, blocks, self.syms, per_f, src, starts, sizes, off, K, words, None), b.index_base)
         return ModelBatch(b.var_widths, self.rows(), b.funcs, b.entry_ptr, b.entry_words, b.entry_base,
                           b.else_words, b.else_base, b.index_base)
 
@@ -434,7 +612,12 @@ class CandidateGenerator:
     """Generates up to ``max_candidates`` candidates for a batch of conjunctions (seeded)."""
 
     def __init__(self, max_candidates: int = 100_000, seed: int = 0, random_frac: float = 0.05, per_query: int = 16,
-                 fill: bool = False, device_rows: bool = False):
+                 fill: bool = False, device_rows: bool = False, device_tables: bool = False):
+        if device_tables and not device_rows:
+            raise ValueError("device_tables needs device_rows: the derived tables read the derived rows")
+        # the candidates' function tables are not materialised either: the set carries a
+        # TableDerivation next to the Derivation (needs device_rows)
+        self.device_tables = bool(device_tables)
         self.max_candidates = int(max_candidates)
         # the candidates' variable rows are not materialised: the set carries a Derivation for
         # Evaluator.upload_models_derived (VerdictEngine.candidate_first_hits, one device)
@@ -591,109 +774,13 @@ class CandidateGenerator:
                 cs._row_args = (lru, src, starts, sizes, blocks, off, K)
             return cs
         if not lru.funcs:
-            return done(ModelBatch(lru.var_widths, words, n_models=M))
-        # function tables: the base model's entries, preceded by an entry for every derived variable
-        # of that function the candidate's patch changed (so table and derived column agree; first
-        # match wins)
-        F = len(lru.funcs)
-        func_index = {name: f for f, name in enumerate(syms.func_names)}
-        dfunc = {v: func_index[fn] for v, (fn, _) in syms.derived.items() if fn in func_index}
-        # per function: (block, position among the block's changed derived vars of it, var) triples
-        per_f: Dict[int, Tuple[List[int], List[int], List[int]]] = {}
-        for j, (patch, _) in enumerate(blocks):
-            vs = {el[0] for el in patch if el[0] in dfunc and el[1] >= 0}
-            if not vs:
-                continue
-            pos: Dict[int, int] = {}
-            for v in sorted(vs):
-                f = dfunc[v]
-                t = per_f.setdefault(f, ([], [], []))
-                t[0].append(j)
-                t[1].append(pos.get(f, 0))
-                t[2].append(v)
-                pos[f] = pos.get(f, 0) + 1
-        eptr = np.zeros((F, M + 1), np.int64)
-        ew_chunks, el_chunks = [], []
-        ebase = np.zeros(F, np.int64)
-        elb = np.zeros(F, np.int64)
-        wpos = epos = 0
-        for f, spec in enumerate(lru.funcs):
-            s = spec.stride
-            base_ptr = lru.entry_ptr[f]
-            base_cnt = np.diff(base_ptr)                                   # [n_lru]
-            cnt_gen = base_cnt[src] if n_lru else np.zeros(K, np.int64)
-            trip = per_f.get(f)
-            if trip is not None:
-                tj, ti, tv = (np.asarray(x, np.int64) for x in trip)
-                add_cnt = np.repeat(np.bincount(tj, minlength=len(blocks)), sizes)
-            else:
-                add_cnt = np.zeros(K, np.int64)
-            counts = np.concatenate([base_cnt, cnt_gen + add_cnt])
-            eptr[f, 1:] = np.cumsum(counts)
-            ent = lru.entry_words[int(lru.entry_base[f]):int(lru.entry_base[f]) + int(base_ptr[-1]) * s].reshape(-1, s)
-            out = np.zeros((int(eptr[f, -1]), s), np.uint32)
-            out[:int(base_ptr[-1])] = ent
-            gstarts = eptr[f, n_lru:n_lru + K]
-            if trip is not None:
-                # the changed derived vars' entries (key = their constant arguments, value = the
-                # candidate's patched column), one row per (triple, candidate of its block)
-                lens = sizes[tj]
-                rep = np.repeat(np.arange(len(tj)), lens)
-                within = np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
-                cols = starts[tj][rep] + within
-                rows = gstarts[cols] + ti[rep]
-                uv, vinv = np.unique(tv, return_inverse=True)
-                keys = np.asarray([[w for aw, av in zip(spec.arg_widths, syms.derived[int(v)][1])
-                                    for w in to_words(int(av), aw)] for v in uv], np.uint32)
-                klen = keys.shape[1]
-                nl = limbs(syms.var_widths[int(uv[0])])
-                out[rows, :klen] = keys[vinv[rep]]
-                vrow = off[uv][vinv[rep]]
-                if words is not None:
-                    out[rows, klen:klen + nl] = words[vrow[:, None] + np.arange(nl)[None, :], (n_lru + cols)[:, None]]
-                else:
-                    # the same values without the matrix: the base model's limbs of that variable
-                    # under the block's composed (keep, bits), then its floor
-                    keep_t = np.full((len(tj), nl), 0xFFFFFFFF, np.uint32)
-                    bits_t = np.zeros((len(tj), nl), np.uint32)
-                    mins_t = np.zeros(len(tj), np.uint32)
-                    for t, (j, v) in enumerate(zip(trip[0], trip[2])):
-                        prow, pfl = composed[j]
-                        for i in range(nl):
-                            c = prow.get(int(off[v]) + i)
-                            if c is not None:
-                                keep_t[t, i], bits_t[t, i] = ~c[0] & 0xFFFFFFFF, c[1]
-                        mins_t[t] = pfl.get(v, 0)
-                    if n_lru:
-                        vals = lru.var_words[vrow[:, None] + np.arange(nl)[None, :], src[cols][:, None]]
-                    else:
-                        vals = np.zeros((len(cols), nl), np.uint32)
-                    vals = (vals & keep_t[rep]) | bits_t[rep]
-                    mn = mins_t[rep]
-                    if mn.any():
-                        small = ~vals[:, 1:].any(axis=1)
-                        vals[:, 0] = np.where(small & (vals[:, 0] < mn), mn, vals[:, 0])
-                    out[rows, klen:klen + nl] = vals
-            if n_lru and K:
-                gstart = gstarts + add_cnt
-                rep = cnt_gen
-                tot = int(rep.sum())
-                if tot:
-                    cand = np.repeat(np.arange(K), rep)
-                    within = np.arange(tot) - np.repeat(np.cumsum(rep) - rep, rep)
-                    dst = gstart[cand] + within
-                    srcrow = base_ptr[src[cand]] + within
-                    out[dst] = ent[srcrow]
-            ebase[f] = wpos
-            ew_chunks.append(out.reshape(-1))
-            wpos += out.size
-            nr = limbs(spec.result_width)
-            lel = lru.else_words[int(lru.else_base[f]):int(lru.else_base[f]) + n_lru * nr].reshape(-1, nr) \
-                if n_lru else np.zeros((0, nr), np.uint32)
-            gel = lel[src] if n_lru else np.zeros((K, nr), np.uint32)
-            elb[f] = epos
-            el = np.concatenate([lel, gel]).reshape(-1)
-            el_chunks.append(el)
-            epos += el.size
-        return done(ModelBatch(lru.var_widths, words, lru.funcs, eptr, np.concatenate(ew_chunks), ebase,
-                               np.concatenate(el_chunks), elb, 0, n_models=M))
+            return done(ModelBatch(lru.var_widths, words, n_models=M, tables=not self.device_tables))
+        per_f = _table_triples(lru, blocks, syms)
+        if self.device_tables:
+            # the tables stay a description too (TableDerivation): the LRU's own tables, and per
+            # block the (function, variable, key) of each entry its patch adds
+            cs = done(ModelBatch(lru.var_widths, None, lru.funcs, n_models=M, tables=False))
+            cs.table_derivation = table_derivation_arrays(lru, len(blocks), per_f, syms)
+            return cs
+        eptr, ew, ebase, el, elb = _function_tables(lru, blocks, syms, per_f, src, starts, sizes, off, K, words, composed)
+        return done(ModelBatch(lru.var_widths, words, lru.funcs, eptr, ew, ebase, el, elb, 0, n_models=M))

@@ -372,6 +372,14 @@ struct mq_ctx {
   DevBuf mpack;     // UploadPack block of the model batch's small tables (upload_one: the views above point in)
   // a derived upload's base rows and derivation tables (views into mpack, read by launch_derive_rows)
   DevBuf dv_base, dv_src, dv_bstart, dv_pptr, dv_patches, dv_fptr, dv_floors;
+  // a derived-table upload's inputs (views into mpack, read by launch_derive_tables) ...
+  DevBuf dt_bptr, dt_bbase, dt_bentries, dt_belse, dt_addptr, dt_adds, dt_addcnt, dt_keys;
+  // ... and the tables the device writes, which no host data is staged into: buffers of their own,
+  // kept across uploads like vars (entry_ptr / entry_words / else_words / dense_words view them)
+  DevBuf dt_entry_ptr, dt_entry_words, dt_else, dt_dense;
+  uint64_t table_uploads = 0;   // derived-table uploads taken
+  std::vector<FuncDev> funcs_dev_h;   // host copy of `funcs` (mq_models_download_funcs)
+  int64_t else_words_n = 0, dense_words_n = 0;
   // Bool variables as packed lane masks [tile][n_bmask] (G kernel PUSH_PKB): bmask_of_var[v] =
   // mask index of Bool variable v (-1: none); bmask_rows[j] = its variable row
   std::vector<int32_t> bmask_of_var;
@@ -997,8 +1005,16 @@ void mq_ctx_destroy(mq_ctx* c) {
 // Upload a model batch to ONE device (n_models may be 0: an empty shard evaluates to "no hit").
 // dv (mq_models_upload_derived, checked by mq_derivation_check): the variable rows are not
 // mb->var_words but dv's base rows and tables, expanded on the device; everything else is shared.
-static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* dv = nullptr) {
+// td / ts (mq_models_upload_derived_tables, checked by mq_table_derivation_check): the function
+// tables are not mb's arrays either; the host only sizes them (ts) and the device writes them.
+struct TableSizes {
+  std::vector<int32_t> add_cnt;          // [F][n_blocks] additions of block j to function f
+  std::vector<int64_t> total, emax;      // [F] entries over all models / the most in one model
+};
+static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* dv = nullptr,
+                      const mq_table_derivation* td = nullptr, const TableSizes* ts = nullptr) {
   if (!c || !mb || mb->n_models < 0 || mb->n_vars < 0 || mb->n_funcs < 0) return MQ_ERR_ARG;
+  if (mb->n_funcs == 0) td = nullptr;   // (no tables to derive)
   if (mb->n_models > 0x7FFFFFFF || mb->index_base + mb->n_models > 0x7FFFFFFE) return MQ_ERR_ARG;
   HIPCHK(hipSetDevice(c->device));
   const int64_t M = mb->n_models;
@@ -1014,7 +1030,7 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   const int F = mb->n_funcs;
   std::vector<FuncDev> fd(std::max(F, 1));
   std::vector<uint32_t> else_soa;
-  int64_t ew_total = 0;
+  int64_t ew_total = 0, else_n = 0, max_words = 0;
   for (int f = 0; f < F; f++) {
     const mq_func_desc& d = mb->funcs[f];
     if (d.arity < 1 || d.arity > 2) return MQ_ERR_ARG;
@@ -1024,8 +1040,17 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
     x.nl_a1 = d.arity > 1 ? nl_of(d.arg_width[1]) : 0;
     x.nl_res = nl_of(d.result_width);
     x.stride = x.nl_a0 + x.nl_a1 + x.nl_res;
-    x.entry_base = mb->entry_base[f];
+    x.entry_base = td ? 0 : mb->entry_base[f];   // (td: mb has no per-model arrays)
     x.ptr_base = (int64_t)f * (M + 1);
+    if (td) {
+      // the materialised batch's layout: functions packed in order
+      x.entry_base = ew_total;
+      x.else_base = else_n;
+      ew_total += ts->total[f] * (int64_t)x.stride;
+      else_n += (int64_t)x.nl_res * M;
+      max_words = std::max(max_words, ts->total[f] * (int64_t)x.stride);
+      continue;
+    }
     x.else_base = (int64_t)else_soa.size();
     const uint32_t* ew = mb->else_words + mb->else_base[f];
     const size_t start = else_soa.size();
@@ -1042,19 +1067,25 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   // entries as slot-major SoA rows as well, so the 64 lanes of a wave probing slot e read one
   // coalesced row per key limb instead of 64 scattered entries.  MQ_NO_DENSE_TABLES=1: off.
   std::vector<uint32_t> dense;
+  int64_t dense_n = 0;   // (td: sized here, written by the device)
   {
     const bool no_dense = std::getenv("MQ_NO_DENSE_TABLES") != nullptr;
     for (int f = 0; f < F && !no_dense && M > 0; f++) {
       FuncDev& x = fd[f];
       if (x.arity != 1 || x.nl_a0 > 8 || x.nl_res > 8) continue;
-      const int64_t* ep = mb->entry_ptr + (int64_t)f * (M + 1);
-      int64_t emax = 0;
-      for (int64_t m = 0; m < M; m++) emax = std::max(emax, ep[m + 1] - ep[m]);
-      const int64_t total = ep[M] - ep[0];
+      const int64_t* ep = td ? nullptr : mb->entry_ptr + (int64_t)f * (M + 1);
+      int64_t emax = td ? ts->emax[f] : 0;
+      for (int64_t m = 0; m < M && !td; m++) emax = std::max(emax, ep[m + 1] - ep[m]);
+      const int64_t total = td ? ts->total[f] : ep[M] - ep[0];
       const int64_t words = emax * (int64_t)(x.nl_a0 + x.nl_res) * M;
       // bounded: at most kDenseMaxE slots, and not much more memory than the CSR entries
       if (emax == 0 || emax > kDenseMaxE || words > 2 * total * (int64_t)x.stride + 16 * M) continue;
       x.dense_e = (uint32_t)emax;
+      if (td) {
+        x.dense_base = dense_n;
+        dense_n += words;
+        continue;
+      }
       x.dense_base = (int64_t)dense.size();
       dense.resize(dense.size() + (size_t)words, 0);
       uint32_t* kd = dense.data() + x.dense_base;
@@ -1076,7 +1107,9 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   UploadPack pk;
   // variable rows followed by one all-zero row (the QSA preload points absent limbs at it)
   HIPCHK(c->vars.ensure(sizeof(uint32_t) * (size_t)(rows + 1) * M));
-  for (DevBuf* b : {&c->dv_base, &c->dv_src, &c->dv_bstart, &c->dv_pptr, &c->dv_patches, &c->dv_fptr, &c->dv_floors})
+  for (DevBuf* b : {&c->dv_base, &c->dv_src, &c->dv_bstart, &c->dv_pptr, &c->dv_patches, &c->dv_fptr, &c->dv_floors,
+                    &c->dt_bptr, &c->dt_bbase, &c->dt_bentries, &c->dt_belse, &c->dt_addptr, &c->dt_adds, &c->dt_addcnt,
+                    &c->dt_keys})
     b->release();   // (views of the previous derived upload's block)
   if (dv) {
     // the base rows and the derivation tables ride in the staged block; the rows themselves are
@@ -1178,7 +1211,42 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   pk.add(c->var_off, voff.data(), voff.size());
   pk.add(c->var_nl, vnl.data(), vnl.size());
   pk.add(c->funcs, fd.data(), fd.size());
-  if (F > 0) {
+  c->funcs_dev_h.assign(fd.begin(), fd.begin() + F);
+  c->else_words_n = 0;
+  for (int f = 0; f < F; f++) c->else_words_n += (int64_t)fd[f].nl_res * M;
+  c->dense_words_n = td ? dense_n : (dense.size() > 1 ? (int64_t)dense.size() : 0);
+  if (td) {
+    // the base models' tables (row pointers from 0, entries and else values packed per function),
+    // the additions and the key pool ride in the staged block
+    const int64_t nb = dv->n_base, nblk = dv->n_blocks;
+    const mq_model_batch* bb = td->base;
+    std::vector<int64_t> bptr((size_t)F * (nb + 1)), bbase(2 * (size_t)F);
+    std::vector<uint32_t> bent, bels;
+    for (int f = 0; f < F; f++) {
+      const int64_t* p = bb->entry_ptr + (int64_t)f * (nb + 1);
+      for (int64_t m = 0; m <= nb; m++) bptr[(size_t)f * (nb + 1) + m] = p[m] - p[0];
+      bbase[2 * f] = (int64_t)bent.size();
+      bbase[2 * f + 1] = (int64_t)bels.size();
+      if (p[nb] > p[0]) {
+        const uint32_t* e0 = bb->entry_words + bb->entry_base[f] + p[0] * (int64_t)fd[f].stride;
+        bent.insert(bent.end(), e0, e0 + (p[nb] - p[0]) * (int64_t)fd[f].stride);
+      }
+      if (nb > 0) bels.insert(bels.end(), bb->else_words + bb->else_base[f], bb->else_words + bb->else_base[f] + nb * (int64_t)fd[f].nl_res);
+    }
+    const int64_t z2[2] = {0, 0};
+    pk.add(c->dt_bptr, bptr.data(), bptr.size());
+    pk.add(c->dt_bbase, bbase.data(), bbase.size());
+    pk.add(c->dt_bentries, bent.data(), bent.size(), 1);
+    pk.add(c->dt_belse, bels.data(), bels.size(), 1);
+    pk.add(c->dt_addptr, nblk ? td->add_ptr : z2, (size_t)nblk + 1);
+    pk.add(c->dt_adds, td->adds, nblk ? (size_t)td->add_ptr[nblk] : 0, 1);
+    pk.add(c->dt_addcnt, ts->add_cnt.data(), ts->add_cnt.size(), 1);
+    pk.add(c->dt_keys, td->key_words, td->key_words ? (size_t)std::max<int64_t>(td->n_key_words, 0) : 0, 1);
+    HIPCHK(c->dt_entry_ptr.ensure(sizeof(int64_t) * (size_t)F * (M + 1)));
+    HIPCHK(c->dt_entry_words.ensure(sizeof(uint32_t) * ((size_t)std::max<int64_t>(ew_total, 1) + kEntryPadWords)));
+    HIPCHK(c->dt_else.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(else_n, 1)));
+    HIPCHK(c->dt_dense.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(dense_n, 1)));
+  } else if (F > 0) {
     pk.add(c->entry_ptr, mb->entry_ptr, (size_t)F * (M + 1));
     // (padded: G's table scan reads the first word of up to 7 entries past a model's last one,
     // gen_qsa.py sub_uf1)
@@ -1189,8 +1257,10 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
     pk.add(c->entry_ptr, &z, 1);
     pk.add(c->entry_words, &zw, 1, kEntryPadWords);
   }
-  pk.add(c->else_words, else_soa.data(), else_soa.size());
-  pk.add(c->dense_words, dense.data(), dense.size());
+  if (!td) {
+    pk.add(c->else_words, else_soa.data(), else_soa.size());
+    pk.add(c->dense_words, dense.data(), dense.size());
+  }
   HIPCHK(pk.commit(c->mpack, c->stream, c->stage));
   if (dv)
     HIPCHK(launch_derive_rows(c->vars.as<uint32_t>(), c->dv_base.as<uint32_t>(), c->dv_src.as<int32_t>(),
@@ -1201,6 +1271,42 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   if (need_mask) HIPCHK(launch_mask_rows(c->vars.as<uint32_t>(), c->rowmask.as<uint32_t>(), rows, M, c->stream));
   HIPCHK(launch_pack_bool(c->vars.as<uint32_t>(), c->bmasks.as<uint64_t>(), c->bmask_rows.as<uint32_t>(), nullptr,
                           c->n_bmask, c->n_bmask, M, c->stream));
+  if (td) {
+    // the tables, from the masked rows: the pad words past the entries and the dense block are
+    // zeroed here, everything else is written by the kernels
+    const size_t ew_words = (size_t)std::max<int64_t>(ew_total, 1) + kEntryPadWords;
+    c->entry_ptr.set_view(c->dt_entry_ptr.p, sizeof(int64_t) * (size_t)F * (M + 1));
+    c->entry_words.set_view(c->dt_entry_words.p, sizeof(uint32_t) * ew_words);
+    c->else_words.set_view(c->dt_else.p, sizeof(uint32_t) * (size_t)std::max<int64_t>(else_n, 1));
+    c->dense_words.set_view(c->dt_dense.p, sizeof(uint32_t) * (size_t)std::max<int64_t>(dense_n, 1));
+    HIPCHK(hipMemsetAsync(c->entry_words.as<uint32_t>() + ew_total, 0, sizeof(uint32_t) * (ew_words - (size_t)ew_total), c->stream));
+    HIPCHK(hipMemsetAsync(c->dense_words.p, 0, c->dense_words.bytes, c->stream));
+    if (else_n == 0) HIPCHK(hipMemsetAsync(c->else_words.p, 0, sizeof(uint32_t), c->stream));
+    TableDerive a{};
+    a.funcs = c->funcs.as<FuncDev>();
+    a.b_ptr = c->dt_bptr.as<int64_t>();
+    a.b_base = c->dt_bbase.as<int64_t>();
+    a.b_entries = c->dt_bentries.as<uint32_t>();
+    a.b_else = c->dt_belse.as<uint32_t>();
+    a.src = c->dv_src.as<int32_t>();
+    a.block_start = c->dv_bstart.as<int64_t>();
+    a.add_ptr = c->dt_addptr.as<int64_t>();
+    a.adds = c->dt_adds.as<TableAdd>();
+    a.add_cnt = c->dt_addcnt.as<int32_t>();
+    a.keys = c->dt_keys.as<uint32_t>();
+    a.vars = c->vars.as<uint32_t>();
+    a.var_off = c->var_off.as<uint32_t>();
+    a.entry_ptr = c->entry_ptr.as<int64_t>();
+    a.entry_words = c->entry_words.as<uint32_t>();
+    a.else_words = c->else_words.as<uint32_t>();
+    a.dense_words = c->dense_words.as<uint32_t>();
+    a.n_base = dv->n_base;
+    a.K = dv->n_derived;
+    a.n_blocks = dv->n_blocks;
+    a.n_funcs = F;
+    HIPCHK(launch_derive_tables(a, max_words, dense_n > 0, c->stream));
+    c->table_uploads++;
+  }
   c->M = M;
   c->index_base = mb->index_base;
   c->n_vars = mb->n_vars;
@@ -1267,9 +1373,11 @@ void mq_models_shard_free(void* handle) { delete static_cast<ShardBuffers*>(hand
 static constexpr int64_t kWideMaxEntries = 64;
 
 // Per-batch bookkeeping every upload entry point does on all devices of the context.
-static void note_batch(mq_ctx* c, const mq_model_batch* mb) {
+static void note_batch(mq_ctx* c, const mq_model_batch* mb, const std::vector<int64_t>* sized = nullptr) {
   std::vector<int64_t> mx((size_t)std::max(mb->n_funcs, 0), 0);
-  if (mb->entry_ptr)
+  if (sized)
+    mx = *sized;
+  else if (mb->entry_ptr)
     for (int f = 0; f < mb->n_funcs; f++) {
       const int64_t* p = mb->entry_ptr + (int64_t)f * (mb->n_models + 1);
       for (int64_t m = 0; m < mb->n_models; m++) mx[f] = std::max(mx[f], p[m + 1] - p[m]);
@@ -1315,11 +1423,148 @@ int mq_models_upload_derived(mq_ctx* c, const mq_model_batch* mb, const mq_deriv
   // (host checks first: a malformed call answers before any device call)
   if (mq_derivation_check(mb, d) != MQ_OK) return MQ_ERR_ARG;
   if (!c || !c->peers.empty()) return MQ_ERR_ARG;
+  // (a description without tables belongs to mq_models_upload_derived_tables)
+  if (mb->n_funcs > 0 && (!mb->funcs || !mb->entry_ptr || !mb->entry_base || !mb->else_base || !mb->else_words)) return MQ_ERR_ARG;
   PhaseTimer pt(&c->host_t[8]);
   note_batch(c, mb);
   c->shard_lo.assign(1, 0);
   c->M_total = mb->n_models;
   return upload_one(c, mb, d);
+}
+
+static_assert(sizeof(mq_table_add) == sizeof(TableAdd) && sizeof(mq_table_add) == 16, "the additions go to the device as they are");
+
+int mq_table_scan_threads(void) { return kTableScanThreads; }
+
+int mq_table_derivation_check(const mq_model_batch* mb, const mq_derivation* d, const mq_table_derivation* t) {
+  if (mq_derivation_check(mb, d) != MQ_OK || !t || mb->n_funcs < 0 || (mb->n_funcs > 0 && !mb->funcs)) return MQ_ERR_ARG;
+  const int F = mb->n_funcs;
+  const int64_t nb = d->n_base, nblk = d->n_blocks;
+  for (int f = 0; f < F; f++)
+    if (mb->funcs[f].arity < 1 || mb->funcs[f].arity > 2) return MQ_ERR_ARG;
+  auto stride_of = [&](int f) {
+    const mq_func_desc& x = mb->funcs[f];
+    return (int64_t)nl_of(x.arg_width[0]) + (x.arity > 1 ? nl_of(x.arg_width[1]) : 0) + nl_of(x.result_width);
+  };
+  // the base models' tables
+  const mq_model_batch* b = t->base;
+  if (!b || b->n_models != nb || b->n_funcs != F) return MQ_ERR_ARG;
+  if (F > 0 && (!b->entry_ptr || !b->entry_base || (nb > 0 && (!b->else_base || !b->else_words)))) return MQ_ERR_ARG;
+  for (int f = 0; f < F; f++) {
+    const int64_t* p = b->entry_ptr + (int64_t)f * (nb + 1);
+    if (p[0] < 0) return MQ_ERR_ARG;
+    for (int64_t m = 0; m < nb; m++)
+      if (p[m + 1] < p[m]) return MQ_ERR_ARG;
+    if (b->entry_base[f] < 0 || b->entry_base[f] + p[nb] * stride_of(f) > b->n_entry_words) return MQ_ERR_ARG;
+    if (p[nb] > p[0] && !b->entry_words) return MQ_ERR_ARG;
+    if (nb > 0 && (b->else_base[f] < 0 || b->else_base[f] + nb * (int64_t)nl_of(mb->funcs[f].result_width) > b->n_else_words))
+      return MQ_ERR_ARG;
+  }
+  // the additions
+  if (nblk == 0) return MQ_OK;
+  if (!t->add_ptr || t->add_ptr[0] != 0) return MQ_ERR_ARG;
+  for (int64_t j = 0; j < nblk; j++)
+    if (t->add_ptr[j + 1] < t->add_ptr[j]) return MQ_ERR_ARG;
+  const int64_t na = t->add_ptr[nblk];
+  if (na > 0 && (!t->adds || !t->key_words || t->n_key_words < 0)) return MQ_ERR_ARG;
+  for (int64_t q = 0; q < na; q++) {
+    const mq_table_add& a = t->adds[q];
+    if (a.func < 0 || a.func >= F || a.var < 0 || a.var >= mb->n_vars) return MQ_ERR_ARG;
+    const mq_func_desc& x = mb->funcs[a.func];
+    if (nl_of(mb->var_width[a.var]) != nl_of(x.result_width)) return MQ_ERR_ARG;
+    const int64_t klen = stride_of(a.func) - nl_of(x.result_width);
+    if (a.key_off < 0 || a.key_off > t->n_key_words - klen) return MQ_ERR_ARG;
+  }
+  for (int64_t j = 0; j < nblk; j++)   // (a block adds a handful of entries: pairwise)
+    for (int64_t q = t->add_ptr[j]; q < t->add_ptr[j + 1]; q++)
+      for (int64_t r = t->add_ptr[j]; r < q; r++)
+        if (t->adds[r].func == t->adds[q].func && t->adds[r].var == t->adds[q].var) return MQ_ERR_ARG;
+  return MQ_OK;
+}
+
+// Per function the total entry count and the largest per-model count of the derived tables, from
+// the base counts, src and the per-block addition counts: O(F * (K + additions)) integer adds.
+static void derived_table_sizes(const mq_model_batch* mb, const mq_derivation* d, const mq_table_derivation* t, TableSizes& s) {
+  const int F = mb->n_funcs;
+  const int64_t nb = d->n_base, nblk = d->n_blocks;
+  s.add_cnt.assign((size_t)F * (size_t)nblk, 0);
+  s.total.assign((size_t)F, 0);
+  s.emax.assign((size_t)F, 0);
+  for (int64_t j = 0; j < nblk; j++)
+    for (int64_t q = t->add_ptr[j]; q < t->add_ptr[j + 1]; q++) s.add_cnt[(size_t)t->adds[q].func * nblk + j]++;
+  for (int f = 0; f < F; f++) {
+    const int64_t* p = t->base->entry_ptr + (int64_t)f * (nb + 1);
+    int64_t total = p[nb] - p[0], emax = 0;
+    for (int64_t m = 0; m < nb; m++) emax = std::max(emax, p[m + 1] - p[m]);
+    for (int64_t j = 0; j < nblk; j++) {
+      const int64_t add = s.add_cnt[(size_t)f * nblk + j];
+      for (int64_t k = d->block_start[j]; k < d->block_start[j + 1]; k++) {
+        const int64_t n = add + (d->src[k] >= 0 ? p[d->src[k] + 1] - p[d->src[k]] : 0);
+        total += n;
+        emax = std::max(emax, n);
+      }
+    }
+    s.total[f] = total;
+    s.emax[f] = emax;
+  }
+}
+
+int mq_models_upload_derived_tables(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* d,
+                                    const mq_table_derivation* t) {
+  // (host checks first: a malformed call answers before any device call)
+  if (mq_table_derivation_check(mb, d, t) != MQ_OK) return MQ_ERR_ARG;
+  if (!c || !c->peers.empty()) return MQ_ERR_ARG;
+  PhaseTimer pt(&c->host_t[8]);
+  TableSizes ts;
+  derived_table_sizes(mb, d, t, ts);
+  note_batch(c, mb, &ts.emax);
+  c->shard_lo.assign(1, 0);
+  c->M_total = mb->n_models;
+  return upload_one(c, mb, d, t, &ts);
+}
+
+int mq_models_funcs_sizes(mq_ctx* c, int64_t sizes[4]) {
+  if (!c || !c->peers.empty() || !sizes) return MQ_ERR_ARG;
+  if (!c->have_models) return MQ_ERR_NO_MODELS;
+  sizes[0] = (int64_t)c->n_funcs * (c->M + 1);
+  sizes[1] = c->n_funcs > 0 ? c->entry_words_n + (int64_t)kEntryPadWords : 0;
+  sizes[2] = c->else_words_n;
+  sizes[3] = c->dense_words_n;
+  return MQ_OK;
+}
+
+int mq_models_download_funcs(mq_ctx* c, int64_t* entry_ptr, uint32_t* entry_words, uint32_t* else_words,
+                             uint32_t* dense_words, int64_t* info, const int64_t sizes[4]) {
+  int64_t want[4];
+  const int rc = mq_models_funcs_sizes(c, want);
+  if (rc != MQ_OK) return rc;
+  if (!sizes || std::memcmp(want, sizes, sizeof want) != 0) return MQ_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<uint32_t> soa;
+  if (entry_ptr && want[0]) HIPCHK(hipMemcpyAsync(entry_ptr, c->entry_ptr.p, sizeof(int64_t) * (size_t)want[0], hipMemcpyDeviceToHost, c->stream));
+  if (entry_words && want[1]) HIPCHK(hipMemcpyAsync(entry_words, c->entry_words.p, sizeof(uint32_t) * (size_t)want[1], hipMemcpyDeviceToHost, c->stream));
+  if (dense_words && want[3]) HIPCHK(hipMemcpyAsync(dense_words, c->dense_words.p, sizeof(uint32_t) * (size_t)want[3], hipMemcpyDeviceToHost, c->stream));
+  if (else_words && want[2]) {
+    soa.resize((size_t)want[2]);
+    HIPCHK(hipMemcpyAsync(soa.data(), c->else_words.p, sizeof(uint32_t) * soa.size(), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  int64_t pos = 0;
+  for (int f = 0; f < c->n_funcs; f++) {
+    const FuncDev& x = c->funcs_dev_h[f];
+    if (else_words && want[2])
+      for (int64_t m = 0; m < c->M; m++)
+        for (uint32_t l = 0; l < x.nl_res; l++) else_words[pos + m * x.nl_res + l] = soa[(size_t)x.else_base + (size_t)l * c->M + m];
+    pos += (int64_t)x.nl_res * c->M;
+    if (info) {
+      info[5 * f] = x.entry_base;
+      info[5 * f + 1] = x.dense_e;
+      info[5 * f + 2] = x.dense_e ? x.dense_base : 0;
+      info[5 * f + 3] = (size_t)f < c->func_max_entries.size() ? c->func_max_entries[f] : 0;
+      info[5 * f + 4] = x.else_base;
+    }
+  }
+  return MQ_OK;
 }
 
 int mq_models_download_vars(mq_ctx* c, uint32_t* out, int64_t n_words) {

@@ -1133,6 +1133,151 @@ hipError_t launch_derive_rows(uint32_t* vars, const uint32_t* base, const int32_
   return hipGetLastError();
 }
 
+// Derived function tables (qs_launch.h TableDerive).  Four kernels on one stream, each reading
+// what the one before wrote: row pointers (count + scan), entry words, else values, dense slots.
+
+// entries of function f in model m: a base model's own, or its source's plus its block's additions
+__device__ __forceinline__ int64_t table_count(const TableDerive& a, int f, int64_t m) {
+  const int64_t* bp = a.b_ptr + (int64_t)f * (a.n_base + 1);
+  if (m < a.n_base) return bp[m + 1] - bp[m];
+  const int64_t k = m - a.n_base;
+  const int32_t s = a.src[k];
+  const int j = derive_block_of(a.block_start, a.n_blocks, k);
+  return (s >= 0 ? bp[s + 1] - bp[s] : 0) + (int64_t)a.add_cnt[(int64_t)f * a.n_blocks + j];
+}
+
+// One workgroup per function: exclusive scan of the per-model entry counts into the function's
+// entry_ptr row [M + 1].  Thread t sums its contiguous chunk of models, the chunk sums are scanned
+// across the workgroup (shuffles inside a wave, the four wave totals through LDS), and a second
+// pass over the chunk writes the running offsets.  M is at most a few 10^5, so a chunk is ~10^3
+// counts, each a handful of cached loads.
+__global__ __launch_bounds__(kTableScanThreads) void derive_table_ptr_kernel(TableDerive a) {
+  const int f = blockIdx.x, t = threadIdx.x;
+  const int64_t M = a.n_base + a.K;
+  const int64_t chunk = (M + kTableScanThreads - 1) / kTableScanThreads;
+  const int64_t m0 = (int64_t)t * chunk < M ? (int64_t)t * chunk : M;
+  const int64_t m1 = m0 + chunk < M ? m0 + chunk : M;
+  long long sum = 0;
+  for (int64_t m = m0; m < m1; m++) sum += table_count(a, f, m);
+  const int lane = t & 63, wave = t >> 6;
+  long long inc = sum;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long o = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += o;
+  }
+  __shared__ long long wave_sum[kTableScanThreads / 64];
+  if (lane == 63) wave_sum[wave] = inc;
+  __syncthreads();
+  long long off = inc - sum;
+  for (int w = 0; w < wave; w++) off += wave_sum[w];
+  int64_t* out = a.entry_ptr + a.funcs[f].ptr_base;
+  for (int64_t m = m0; m < m1; m++) {
+    out[m] = off;
+    off += table_count(a, f, m);
+  }
+  if (t == kTableScanThreads - 1) out[M] = off;   // (its chunk ends at M, or is empty: the total)
+}
+
+// One thread per output word (grid-stride along x, function = blockIdx.y), so a wave stores 256
+// contiguous bytes.  The word's model is found by binary search in the row pointers just written.
+__global__ __launch_bounds__(256) void derive_table_entries_kernel(TableDerive a) {
+  const int f = blockIdx.y;
+  const FuncDev fd = a.funcs[f];
+  const int64_t M = a.n_base + a.K;
+  const int64_t* ptr = a.entry_ptr + fd.ptr_base;
+  const int64_t* bp = a.b_ptr + (int64_t)f * (a.n_base + 1);
+  const uint32_t* bent = a.b_entries + a.b_base[2 * f];
+  uint32_t* out = a.entry_words + fd.entry_base;
+  const int64_t stride = fd.stride, klen = fd.nl_a0 + fd.nl_a1;
+  const int64_t nw = ptr[M] * stride;
+  for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < nw; w += (int64_t)gridDim.x * 256) {
+    const int64_t e = w / stride, i = w - e * stride;
+    int64_t lo = 0, hi = M;   // the last model whose first entry is <= e (empty models before it are skipped)
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (ptr[mid] <= e) lo = mid; else hi = mid;
+    }
+    const int64_t m = lo;
+    int64_t local = e - ptr[m], s = m;
+    if (m >= a.n_base) {
+      const int64_t k = m - a.n_base;
+      const int j = derive_block_of(a.block_start, a.n_blocks, k);
+      const int64_t na = a.add_cnt[(int64_t)f * a.n_blocks + j];
+      if (local < na) {
+        // the local-th addition of the block to this function: its key, then the model's limbs
+        uint32_t val = 0;
+        int64_t seen = 0;
+        for (int64_t q = a.add_ptr[j]; q < a.add_ptr[j + 1]; q++) {
+          const TableAdd ad = a.adds[q];
+          if (ad.func != f || seen++ != local) continue;
+          val = i < klen ? a.keys[ad.key_off + i] : a.vars[((size_t)a.var_off[ad.var] + (size_t)(i - klen)) * (size_t)M + (size_t)m];
+          break;
+        }
+        out[w] = val;
+        continue;
+      }
+      local -= na;
+      s = a.src[k];   // (>= 0: a model without a source has no entries past its additions)
+    }
+    out[w] = bent[(bp[s] + local) * stride + i];
+  }
+}
+
+// else values straight into the SoA block, and the dense slots of the functions the host marked
+// dense (slot-major, from the CSR just built): one thread per (function, model), stores coalesced
+// along the model axis.
+__global__ __launch_bounds__(256) void derive_table_else_kernel(TableDerive a) {
+  const int f = blockIdx.y;
+  const FuncDev fd = a.funcs[f];
+  const int64_t M = a.n_base + a.K;
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const int64_t s = m < a.n_base ? m : (int64_t)a.src[m - a.n_base];
+  const uint32_t* be = a.b_else + a.b_base[2 * f + 1];
+  uint32_t* out = a.else_words + fd.else_base;
+  for (uint32_t l = 0; l < fd.nl_res; l++) out[(size_t)l * M + m] = s >= 0 ? be[s * fd.nl_res + l] : 0u;
+}
+
+__global__ __launch_bounds__(256) void derive_table_dense_kernel(TableDerive a) {
+  const int f = blockIdx.y;
+  const FuncDev fd = a.funcs[f];
+  if (fd.dense_e == 0) return;
+  const int64_t M = a.n_base + a.K;
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const int64_t* ptr = a.entry_ptr + fd.ptr_base;
+  const int64_t e0 = ptr[m];
+  int64_t n = ptr[m + 1] - e0;
+  if (n > (int64_t)fd.dense_e) n = fd.dense_e;   // (the host sized dense_e as the largest count)
+  uint32_t* kd = a.dense_words + fd.dense_base;
+  uint32_t* vd = kd + (size_t)fd.dense_e * fd.nl_a0 * (size_t)M;
+  for (int64_t e = 0; e < n; e++) {
+    const uint32_t* ent = a.entry_words + fd.entry_base + (e0 + e) * (int64_t)fd.stride;
+    for (uint32_t l = 0; l < fd.nl_a0; l++) kd[((size_t)e * fd.nl_a0 + l) * (size_t)M + m] = ent[l];
+    for (uint32_t l = 0; l < fd.nl_res; l++) vd[((size_t)e * fd.nl_res + l) * (size_t)M + m] = ent[fd.nl_a0 + l];
+  }
+}
+
+hipError_t launch_derive_tables(const TableDerive& a, int64_t max_words, bool any_dense, hipStream_t st) {
+  const int64_t M = a.n_base + a.K;
+  if (a.n_funcs <= 0) return hipSuccess;
+  if (a.n_funcs > 65535 || (a.K > 0 && a.n_blocks < 1)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(derive_table_ptr_kernel, dim3((unsigned)a.n_funcs), dim3(kTableScanThreads), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || M <= 0) return e;
+  if (max_words > 0) {
+    const int64_t gx = std::min<int64_t>((max_words + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(derive_table_entries_kernel, dim3((unsigned)gx, (unsigned)a.n_funcs), dim3(256), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  const dim3 gm((unsigned)((M + 255) / 256), (unsigned)a.n_funcs);
+  hipLaunchKernelGGL(derive_table_else_kernel, gm, dim3(256), 0, st, a);
+  if ((e = hipGetLastError()) != hipSuccess || !any_dense) return e;
+  hipLaunchKernelGGL(derive_table_dense_kernel, gm, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 __global__ void qs_init_best(int32_t* best, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) best[i] = 0x7FFFFFFF;

@@ -137,6 +137,42 @@ hipError_t launch_derive_rows(uint32_t* vars, const uint32_t* base, const int32_
                               const int64_t* patch_ptr, const RowPatch* patches, const int64_t* floor_ptr,
                               const RowFloor* floors, int64_t n_floors, int64_t n_base, int64_t K, int64_t rows,
                               int32_t n_blocks, hipStream_t st);
+// Derived function tables (mq_models_upload_derived_tables): the CSR row pointers, entry words,
+// SoA else values and dense slots of all M = n_base + K models written on the device from the
+// base models' tables and each block's additions, after the rows are derived and masked (an added
+// entry's value is the model's resident limbs of a variable).  Model m < n_base keeps base model
+// m's entries; derived model k of block j has the block's additions for the function first, in
+// list order, then the entries of base model src[k] (none for -1; else value 0).
+struct TableAdd {   // mq.h's mq_table_add
+  int32_t func, var;
+  int64_t key_off;
+};
+struct TableDerive {
+  const FuncDev* funcs;          // the OUTPUT layout (ptr_base, entry_base, else_base, dense_*), [n_funcs]
+  const int64_t* b_ptr;          // base CSR rows [n_funcs][n_base + 1], each from 0
+  const int64_t* b_base;         // [2 * n_funcs]: word offset of f's entries in b_entries, of its else values in b_else
+  const uint32_t* b_entries;     // base entries, stride words each
+  const uint32_t* b_else;        // base else values, AoS: b_else[b_base[2f+1] + m * nl_res + l]
+  const int32_t* src;            // [K]
+  const int64_t* block_start;    // [n_blocks + 1]
+  const int64_t* add_ptr;        // [n_blocks + 1] into adds
+  const TableAdd* adds;
+  const int32_t* add_cnt;        // [n_funcs][n_blocks]: additions of block j to function f
+  const uint32_t* keys;          // key pool: an addition's constant key words at key_off
+  const uint32_t* vars;          // the resident rows [rows][M], masked
+  const uint32_t* var_off;       // [n_vars] first row of a variable
+  int64_t* entry_ptr;
+  uint32_t* entry_words;
+  uint32_t* else_words;
+  uint32_t* dense_words;         // zeroed by the caller
+  int64_t n_base, K;
+  int32_t n_blocks, n_funcs;
+};
+// threads of the one workgroup per function that scans the entry counts into entry_ptr: thread t
+// owns models [t * chunk, (t + 1) * chunk), chunk = ceil(M / kTableScanThreads)
+constexpr int kTableScanThreads = 256;
+// max_words: the most entry words (entries * stride) any function holds (sizes the entries grid)
+hipError_t launch_derive_tables(const TableDerive& a, int64_t max_words, bool any_dense, hipStream_t st);
 hipError_t launch_finalize_best(int32_t* best, const uint8_t* unsupported, int n, hipStream_t st);
 hipError_t launch_keccak(const uint8_t* data, const int64_t* offsets, int n, uint8_t* out, hipStream_t st);
 

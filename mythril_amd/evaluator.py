@@ -15,8 +15,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ._abi import (MqDagBatch, MqDerivation, MqModelBatch, MqNode, MqStats, MqTapeBatch, as_dag_batch, as_derivation,
-                   as_model_batch, as_tape_batch)
+from ._abi import (MqDagBatch, MqDerivation, MqModelBatch, MqNode, MqStats, MqTableDerivation, MqTapeBatch, as_dag_batch,
+                   as_derivation, as_model_batch, as_table_derivation, as_tape_batch)
 from .models import ModelBatch
 from .tape import TapeBatch
 
@@ -96,6 +96,13 @@ def load_library(path: str = LIB_PATH):
         L.mq_derivation_check.argtypes = [C.POINTER(MqModelBatch), C.POINTER(MqDerivation)]
         L.mq_models_upload_derived.argtypes = [P, C.POINTER(MqModelBatch), C.POINTER(MqDerivation)]
         L.mq_models_download_vars.argtypes = [P, C.POINTER(C.c_uint32), C.c_int64]
+        L.mq_table_derivation_check.argtypes = [C.POINTER(MqModelBatch), C.POINTER(MqDerivation), C.POINTER(MqTableDerivation)]
+        L.mq_models_upload_derived_tables.argtypes = [P, C.POINTER(MqModelBatch), C.POINTER(MqDerivation),
+                                                      C.POINTER(MqTableDerivation)]
+        L.mq_models_funcs_sizes.argtypes = [P, C.POINTER(C.c_int64)]
+        L.mq_models_download_funcs.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mq_table_scan_threads.argtypes = []
         _lib = L
         return L
 
@@ -419,15 +426,25 @@ class Evaluator:
         self.index_base = mb.index_base
         self._var_widths = mb.var_widths
 
-    def upload_models_derived(self, mb: ModelBatch, derivation) -> None:
+    table_uploads = 0   # uploads that took the derived-table path (upload_models_derived with tables)
+
+    def upload_models_derived(self, mb: ModelBatch, derivation, tables=None) -> None:
         """Replace the candidate set with ``derivation``'s base models followed by its derived
         ones, their variable rows expanded on the device (``mq_models_upload_derived``).  ``mb``
         describes all of them as for :meth:`upload_models`; its ``var_words`` may be absent.
-        Single-device evaluators only."""
+        With ``tables`` (a :class:`mythril_amd.candidates.TableDerivation`) the function tables are
+        derived on the device as well (``mq_models_upload_derived_tables``) and ``mb`` needs no
+        per-model array at all.  Single-device evaluators only."""
         s, keep = as_model_batch(mb)
         d, keep_d = as_derivation(derivation)
         self.upload_seq += 1
-        _check(self.lib.mq_models_upload_derived(self.ctx, C.byref(s), C.byref(d)), "mq_models_upload_derived")
+        if tables is not None:
+            t, keep_t = as_table_derivation(tables)
+            _check(self.lib.mq_models_upload_derived_tables(self.ctx, C.byref(s), C.byref(d), C.byref(t)),
+                   "mq_models_upload_derived_tables")
+            self.table_uploads += 1
+        else:
+            _check(self.lib.mq_models_upload_derived(self.ctx, C.byref(s), C.byref(d)), "mq_models_upload_derived")
         self.n_models = mb.n_models
         self.index_base = mb.index_base
         self._var_widths = mb.var_widths
@@ -443,6 +460,28 @@ class Evaluator:
         _check(self.lib.mq_models_download_vars(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size),
                "mq_models_download_vars")
         return out
+
+    def download_funcs(self):
+        """Diagnostic: the resident function tables as a namespace of ``entry_ptr`` int64[F, M + 1],
+        ``entry_words`` (including the zero padding past the last entry), ``else_words`` in the host
+        (AoS) layout of ``mq_model_batch``, ``dense_words`` as resident and ``info`` int64[F, 5] of
+        (entry_base, dense_e, dense_base, largest per-model entry count, SoA else base) per
+        function.  Single-device evaluators only."""
+        from types import SimpleNamespace
+        sizes = (C.c_int64 * 4)()
+        _check(self.lib.mq_models_funcs_sizes(self.ctx, sizes), "mq_models_funcs_sizes")
+        n_ptr, n_ew, n_el, n_dn = (int(x) for x in sizes)
+        F = n_ptr // (self.n_models + 1)
+        eptr = np.zeros(max(n_ptr, 1), np.int64)
+        ew, el, dn = (np.zeros(max(n, 1), np.uint32) for n in (n_ew, n_el, n_dn))
+        info = np.zeros((max(F, 1), 5), np.int64)
+        u32 = C.POINTER(C.c_uint32)
+        _check(self.lib.mq_models_download_funcs(self.ctx, eptr.ctypes.data_as(C.POINTER(C.c_int64)), ew.ctypes.data_as(u32),
+                                                 el.ctypes.data_as(u32), dn.ctypes.data_as(u32),
+                                                 info.ctypes.data_as(C.POINTER(C.c_int64)), sizes),
+               "mq_models_download_funcs")
+        return SimpleNamespace(entry_ptr=eptr[:n_ptr].reshape(F, -1) if F else eptr[:0], entry_words=ew[:n_ew],
+                               else_words=el[:n_el], dense_words=dn[:n_dn], info=info[:F])
 
     # ------------------------------------------------------------ tapes
     def compile(self, tb: TapeBatch) -> CompiledTapes:

@@ -41,7 +41,7 @@ class ModelBatch:
                  funcs: Sequence[FuncSpec] = (), entry_ptr: Optional[np.ndarray] = None,
                  entry_words: Optional[np.ndarray] = None, entry_base: Optional[np.ndarray] = None,
                  else_words: Optional[np.ndarray] = None, else_base: Optional[np.ndarray] = None,
-                 index_base: int = 0, n_models: Optional[int] = None):
+                 index_base: int = 0, n_models: Optional[int] = None, tables: bool = True):
         self.var_widths = np.asarray(var_widths, dtype=np.uint16)
         # limbs(w) per variable (Bool -> 1), vectorised: the drop-in path builds a batch per launch
         n_rows = int(np.maximum((self.var_widths.astype(np.int64) + 31) // 32, 1).sum())
@@ -65,6 +65,14 @@ class ModelBatch:
             self.func_arr[i]["result_width"] = f.result_width
             aw = list(f.arg_widths) + [0] * (2 - len(f.arg_widths))
             self.func_arr[i]["arg_width"] = aw[:2]
+        self.index_base = int(index_base)
+        if not tables:
+            # the function tables are derived on the device too (candidates.TableDerivation): the
+            # batch is the widths and the function signatures, nothing per model
+            if var_words is not None:
+                raise ValueError("a batch without tables has no var_words either")
+            self.entry_ptr = self.entry_words = self.entry_base = self.else_words = self.else_base = None
+            return
         self.entry_ptr = np.ascontiguousarray(entry_ptr if entry_ptr is not None else np.zeros((max(F, 1), M + 1), np.int64), dtype=np.int64)
         self.entry_words = np.ascontiguousarray(entry_words if entry_words is not None else np.zeros(1, np.uint32), dtype=np.uint32)
         self.entry_base = np.ascontiguousarray(entry_base if entry_base is not None else np.zeros(max(F, 1), np.int64), dtype=np.int64)
@@ -74,7 +82,6 @@ class ModelBatch:
             self.entry_words = np.zeros(1, np.uint32)
         if self.else_words.size == 0:
             self.else_words = np.zeros(1, np.uint32)
-        self.index_base = int(index_base)
 
     @property
     def n_vars(self) -> int:

@@ -443,7 +443,8 @@ class VerdictEngine:
             fh, t3, t4 = self._first_hit(db, cs.batch)
         elif len(getattr(self.evaluator, "devices", (0,))) == 1:
             # generator.device_rows: the device expands the candidates' rows from the LRU's
-            fh, t3, t4 = self._first_hit(db, cs.batch, cs.derivation)
+            # (device_tables: the function tables too, from the LRU's and the blocks' additions)
+            fh, t3, t4 = self._first_hit(db, cs.batch, cs.derivation, cs.table_derivation)
         else:
             mb = cs.host_batch()   # (a multi-device context shards host rows)
             t2 = clock()
@@ -458,13 +459,13 @@ class VerdictEngine:
         fh = np.where(ok, fh, -2)
         return fh, cs
 
-    def _first_hit(self, tb, mb, derivation=None):
+    def _first_hit(self, tb, mb, derivation=None, tables=None):
         """Upload + compile + first-hit launch; returns (first hits, time after upload, time
         after compile)."""
         clock = time.perf_counter
         ev = self.evaluator
         if derivation is not None:
-            ev.upload_models_derived(mb, derivation)
+            ev.upload_models_derived(mb, derivation, tables)
         else:
             ev.upload_models(mb)
         t3 = clock()
@@ -768,9 +769,11 @@ class ModelCache:
         if not todo:
             return out
         order = list(reversed(self.model_cache.lru_cache.keys()))
-        # MQ_DEVICE_CANDIDATES=1 (opt-in): the candidates' rows are derived on the device
+        # MQ_DEVICE_CANDIDATES (opt-in): 1 = the candidates' rows are derived on the device,
+        # 2 = their function tables as well
+        mode = os.environ.get("MQ_DEVICE_CANDIDATES")
         gen = CandidateGenerator(args.quick_sat_candidate_budget, seed=len(self.stats) + self.stats["queries"],
-                                 device_rows=os.environ.get("MQ_DEVICE_CANDIDATES") == "1")
+                                 device_rows=mode in ("1", "2"), device_tables=mode == "2")
         fh, cs = self.engine.candidate_first_hits([exprs[i] for i in todo], order, gen)
         for i, h in zip(todo, fh):
             if h < 0:
