@@ -311,6 +311,64 @@ int mq_table_derivation_check(const mq_model_batch* models, const mq_derivation*
 int mq_models_upload_derived_tables(mq_ctx* ctx, const mq_model_batch* models, const mq_derivation* d,
                                     const mq_table_derivation* t);
 
+/* Keccak derivation, passed alongside an mq_derivation and an mq_table_derivation: per "site"
+   (an application keccak256_<n>(x) whose input x is a word-aligned map of model variables) every
+   derived model of a block that activates the site gets, BEHIND its base model's entries and in
+   site order,
+     x -> v          in the site's function `func` (one key of n_words limbs, 256-bit result),
+     v -> x[lo..]    in each of the site's inverses (256-bit key; the value is the result's limbs
+                     of x starting at limb lo_word: keccak256_<n>-1 itself and its value slices),
+   where x is read from the model's resident (patched, floored, masked) rows through the site's
+   word map -- limb l of x is words[map_off + l]: the row `row`, or with row == 0xFFFFFFFF the
+   constant `value` -- and v = base + ((D mod 2^b) << 6), D the keccak256 (Ethereum padding) of
+   x's 4 * n_words big-endian bytes read big-endian (MQ_OP_KECCAK's value), base the 256-bit
+   number of limbs base[0..7].  Collision rule: when x equals the n_words key words at
+   key_words[key_off] of one of the site's collisions, v is instead the model's resident limbs of
+   that collision's (256-bit) variable `var`.
+     active    [n_blocks] of the row derivation's blocks: bit i set = site i is active in the block. */
+typedef struct mq_keccak_word { uint32_t row, value; } mq_keccak_word;
+typedef struct mq_keccak_inverse { int32_t func; uint32_t lo_word; } mq_keccak_inverse;
+typedef struct mq_keccak_collision { int32_t var, pad; int64_t key_off; } mq_keccak_collision;
+typedef struct mq_keccak_site {
+  int32_t func;
+  uint32_t n_words;              /* n / 32, 1..64 */
+  int64_t map_off;               /* first of its n_words entries of `words` */
+  int32_t inv_off, n_inv;        /* its entries of `inverses` */
+  int32_t coll_off, n_coll;      /* its entries of `collisions` (at most 8) */
+  uint32_t b, pad;               /* <= 192 */
+  uint32_t base[8];              /* a multiple of 64 */
+} mq_keccak_site;
+typedef struct mq_keccak_derivation {
+  int32_t n_sites;               /* <= 64 */
+  const mq_keccak_site* sites;
+  const mq_keccak_word* words;
+  int64_t n_words;
+  const mq_keccak_inverse* inverses;
+  int64_t n_inverses;
+  const mq_keccak_collision* collisions;
+  int64_t n_collisions;
+  const uint32_t* key_words;
+  int64_t n_key_words;
+  const uint64_t* active;
+} mq_keccak_derivation;
+
+/* Host-only: MQ_OK when `s` is well formed over `models` and `d` (mq_derivation_check is NOT
+   repeated here): n_sites in 0..64; per site func < n_funcs of arity 1 with a 32 * n_words-bit key
+   and a 256-bit result; every inverse a different function of arity 1 with a 256-bit key whose
+   result is whole limbs lo_word .. lo_word + limbs(result) <= n_words; map entries inside `words`,
+   their rows below the batch's rows; b <= 192, base % 64 == 0 and base + 64 * 2^b <= 2^256;
+   collisions inside their arrays, var < n_vars of 256 bits, key words inside the pool; active
+   masks naming only existing sites.  Else MQ_ERR_ARG. */
+int mq_keccak_derivation_check(const mq_model_batch* models, const mq_derivation* d, const mq_keccak_derivation* s);
+
+/* mq_models_upload_derived_tables with the keccak sites' entries derived on the device as well
+   (one keccak-f[1600] per (derived model, active site)).  All three host checks run before the
+   device is touched (MQ_ERR_ARG leaves the resident models as they were); afterwards the context
+   is indistinguishable from mq_models_upload of the fully materialised batch.  Single-device
+   contexts only. */
+int mq_models_upload_derived_keccak(mq_ctx* ctx, const mq_model_batch* models, const mq_derivation* d,
+                                    const mq_table_derivation* t, const mq_keccak_derivation* s);
+
 /* Diagnostic: the resident function tables.  mq_models_funcs_sizes fills sizes[4] = { words of
    entry_ptr (n_funcs * (M + 1)), entry words INCLUDING the zero padding the table scan may read
    past the last entry, else words, dense-slot words }.  mq_models_download_funcs copies them out,

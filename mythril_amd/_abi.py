@@ -87,6 +87,49 @@ class MqTableDerivation(C.Structure):
     ]
 
 
+class MqKeccakWord(C.Structure):
+    _fields_ = [("row", C.c_uint32), ("value", C.c_uint32)]
+
+
+class MqKeccakInverse(C.Structure):
+    _fields_ = [("func", C.c_int32), ("lo_word", C.c_uint32)]
+
+
+class MqKeccakCollision(C.Structure):
+    _fields_ = [("var", C.c_int32), ("pad", C.c_int32), ("key_off", C.c_int64)]
+
+
+class MqKeccakSite(C.Structure):
+    _fields_ = [
+        ("func", C.c_int32),
+        ("n_words", C.c_uint32),
+        ("map_off", C.c_int64),
+        ("inv_off", C.c_int32),
+        ("n_inv", C.c_int32),
+        ("coll_off", C.c_int32),
+        ("n_coll", C.c_int32),
+        ("b", C.c_uint32),
+        ("pad", C.c_uint32),
+        ("base", C.c_uint32 * 8),
+    ]
+
+
+class MqKeccakDerivation(C.Structure):
+    _fields_ = [
+        ("n_sites", C.c_int32),
+        ("sites", C.POINTER(MqKeccakSite)),
+        ("words", C.POINTER(MqKeccakWord)),
+        ("n_words", C.c_int64),
+        ("inverses", C.POINTER(MqKeccakInverse)),
+        ("n_inverses", C.c_int64),
+        ("collisions", C.POINTER(MqKeccakCollision)),
+        ("n_collisions", C.c_int64),
+        ("key_words", C.POINTER(C.c_uint32)),
+        ("n_key_words", C.c_int64),
+        ("active", C.POINTER(C.c_uint64)),
+    ]
+
+
 class MqStats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_double),
@@ -181,6 +224,41 @@ def as_table_derivation(t):
         return C.cast(a.ctypes.data, C.POINTER(ctype)) if a.size else C.POINTER(ctype)()
     s = MqTableDerivation(C.pointer(base), ptr(ap, C.c_int64), ptr(adds, MqTableAdd), ptr(keys, C.c_uint32), keys.size)
     return s, (base, keep_b, ap, adds, keys)
+
+
+def keccak_derivation_arrays(ks):
+    """The arrays of ``mq_keccak_derivation`` for a :class:`mythril_amd.candidates.KeccakSites`:
+    ``(sites, words, inverses, collisions, key_words, active)`` (structured numpy arrays)."""
+    from .tape import to_words
+    sites = np.zeros(len(ks.sites), np.dtype([("func", "<i4"), ("n_words", "<u4"), ("map_off", "<i8"), ("inv_off", "<i4"),
+                                              ("n_inv", "<i4"), ("coll_off", "<i4"), ("n_coll", "<i4"), ("b", "<u4"),
+                                              ("pad", "<u4"), ("base", "<u4", (8,))]))
+    words, invs, colls, keys = [], [], [], []
+    for i, s in enumerate(ks.sites):
+        sites[i] = (s.func, s.n_bits // 32, len(words), len(invs), len(s.inverses), len(colls), len(s.collisions), s.b, 0,
+                    to_words(s.base, 256))
+        words += [(0xFFFFFFFF, cv) if row < 0 else (row, 0) for row, cv in s.words]
+        invs += [(g, lo // 32) for g, lo, _ in s.inverses]
+        for key, var, _ in s.collisions:
+            colls.append((var, 0, len(keys)))
+            keys += to_words(key, s.n_bits)
+    return (sites, np.asarray(words, np.dtype([("row", "<u4"), ("value", "<u4")])),
+            np.asarray(invs, np.dtype([("func", "<i4"), ("lo_word", "<u4")])),
+            np.asarray(colls, np.dtype([("var", "<i4"), ("pad", "<i4"), ("key_off", "<i8")])),
+            np.asarray(keys, np.uint32), np.ascontiguousarray(ks.active, np.uint64))
+
+
+def as_keccak_derivation(ks, arrays=None):
+    """``mq_keccak_derivation`` over a :class:`mythril_amd.candidates.KeccakSites` (``arrays``: the
+    tuple of :func:`keccak_derivation_arrays`, to pass altered ones)."""
+    sites, words, invs, colls, keys, active = arrays if arrays is not None else keccak_derivation_arrays(ks)
+
+    def ptr(a, ctype):
+        return C.cast(a.ctypes.data, C.POINTER(ctype)) if a.size else C.POINTER(ctype)()
+    s = MqKeccakDerivation(len(sites), ptr(sites, MqKeccakSite), ptr(words, MqKeccakWord), len(words),
+                           ptr(invs, MqKeccakInverse), len(invs), ptr(colls, MqKeccakCollision), len(colls),
+                           ptr(keys, C.c_uint32), keys.size, ptr(active, C.c_uint64))
+    return s, (sites, words, invs, colls, keys, active)
 
 
 def as_dag_batch(db):

@@ -20,7 +20,10 @@ variables), ``Extract``, ``Concat``, ``ZeroExt`` and the calldata-byte shape ``I
 byte, 0)`` (calldata.py:234-246).  Patching a derived variable (the interpretation of
 ``<tx>_calldata`` at a constant index) also adds that entry to the candidate's table, so every
 candidate is a consistent model: evaluating it is exactly ``model.eval(expr, model_completion=
-True)`` of the model :meth:`CandidateSet.materialize` returns.
+True)`` of the model :meth:`CandidateSet.materialize` returns.  With ``keccak_sites`` (opt-in) a
+patch that changes the input of a ``keccak256_<n>`` application also enters the new input's image
+in that function's table and its inverse's (:class:`KeccakSites`), so the keccak manager's axioms
+hold on the candidate and forks over a mapping key can be answered.
 
 Generated candidates sit strictly AFTER the LRU models in global candidate order (index >= the
 LRU size), so an LRU hit is never pre-empted and the reference's first-hit / bump semantics are
@@ -31,13 +34,14 @@ callers (``Constraints.is_possible``), never for callers that read model content
 from __future__ import annotations
 
 import os
+import re
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .models import ModelBatch
 from .smt_model import Model, as_record
-from .tape import limbs, to_words
+from .tape import NONE, Op, Tape, limbs, to_words
 
 _EQ, _ULT, _ULE, _SLT, _SLE = 20, 21, 22, 23, 24
 _PREDS = (_EQ, _ULT, _ULE, _SLT, _SLE)
@@ -398,6 +402,272 @@ def table_derivation_arrays(lru: ModelBatch, n_blocks: int, per_f, syms) -> Tabl
                            [key_off[v] for _, _, v in adds], np.asarray(keys, np.uint32))
 
 
+# ---------------------------------------------------------------------------------------------
+# Keccak sites (opt-in, CandidateGenerator(keccak_sites=True)): a patch that changes a variable
+# feeding keccak256_<n>(x) moves x to an input the base model's tables do not hold, so the
+# manager's axiom keccak256_<n>-1(keccak256_<n>(x)) == x (function_managers.py _create_condition)
+# fails on the else values.  For such an application the candidate gets x -> v appended to
+# keccak256_<n> and v -> x to keccak256_<n>-1 (and its @@lo:hi slice functions), v being the
+# digest of x folded into the manager's interval: base + ((keccak256(x) mod 2^b) << 6).
+_KECCAK_NAME = re.compile(r"keccak256_(\d+)$")
+_UF, _UF_CHUNK, _UF_WIDE, _KECCAK_OP, _OR = (int(o) for o in (Op.UF, Op.UF_CHUNK, Op.UF_WIDE, Op.KECCAK, Op.OR))
+_REFS = {int(o): Tape.operand_slots(o) for o in Op}   # which of (a, b, c) are node references, per op
+MAX_SITES = 64
+MAX_SITE_BITS = 2048
+MAX_COLLISIONS = 8
+
+
+def image_params(lo: int, hi: int) -> Optional[Tuple[int, int]]:
+    """``(base, b)`` of the interval ``[lo, hi)``: base = lo rounded up to a multiple of 64, b the
+    largest integer <= 192 with base + 64 * 2^b <= hi (None: the interval holds no such image)."""
+    base = (lo + 63) & ~63
+    q = (hi - base) // 64
+    if q < 1:
+        return None
+    return base, min(192, q.bit_length() - 1)
+
+
+def keccak_images(xs: Sequence[int], n_bits: int, base: int, b: int) -> List[int]:
+    """The image of each ``n_bits``-wide input: base + ((D mod 2^b) << 6), D the keccak256 (Ethereum
+    padding) of the input's big-endian bytes read big-endian (mq.h MQ_OP_KECCAK)."""
+    from .evaluator import keccak256_host
+    digs = keccak256_host([int(x).to_bytes(n_bits // 8, "big") for x in xs])
+    m = (1 << b) - 1
+    return [base + ((int.from_bytes(d, "big") & m) << 6) for d in digs]
+
+
+class KeccakSite:
+    """One ``keccak256_<n>(x)`` application whose input is a word-aligned map of model variables."""
+
+    def __init__(self, node, func, n_bits, inverses, segs, words, base, b, collisions):
+        self.node = node               # the UF node (sites are ordered by it)
+        self.func = func               # f
+        self.n_bits = n_bits
+        self.inverses = inverses       # [(function id, lo, hi)]: f^-1 (0, n) and its slices, bits [lo, hi) of x
+        self.segs = segs               # the input's bit map (_BitMaps.map)
+        self.words = words             # per 32-bit word of x, low first: (row, 0) or (-1, constant)
+        self.base, self.b = base, b    # image_params of the interval in the DAG
+        self.collisions = collisions   # [(constant key, derived variable of f at that key, its first row)]
+        self.vars = frozenset(v for v, _, _ in segs if v >= 0)
+
+
+class KeccakSites:
+    """The batch's keccak sites and, per block, the 64-bit mask of the sites its patch activates —
+    the arrays of ``mq_keccak_derivation`` (include/mq.h); rides on the CandidateSet next to
+    Derivation / TableDerivation."""
+
+    def __init__(self, sites: List[KeccakSite], active: np.ndarray, skipped: Dict[str, int]):
+        self.sites = sites
+        self.active = np.ascontiguousarray(active, np.uint64)
+        self.skipped = skipped
+
+    def contributions(self, f: int) -> List[Tuple[int, Optional[Tuple[int, int]]]]:
+        """Sites that append an entry to function ``f``, in site order: (site, None) for the site's
+        own function, (site, (lo, hi)) for its inverse or a slice of it."""
+        out = []
+        for i, s in enumerate(self.sites):
+            if s.func == f:
+                out.append((i, None))
+            for g, lo, hi in s.inverses:
+                if g == f:
+                    out.append((i, (lo, hi)))
+        return out
+
+    def site_counts(self, n_funcs: int) -> np.ndarray:
+        """int64[n_funcs, n_blocks]: entries the active sites of block j append to function f."""
+        cnt = np.zeros((n_funcs, len(self.active)), np.int64)
+        for f in range(n_funcs):
+            for i, _ in self.contributions(f):
+                cnt[f] += ((self.active >> np.uint64(i)) & np.uint64(1)).astype(np.int64)
+        return cnt
+
+
+def _reachable(db) -> np.ndarray:
+    """Nodes of the DAG reachable from the batch's roots (ascending)."""
+    op, a, b, c = (db.nodes[k] for k in ("op", "a", "b", "c"))
+    seen = set()
+    stack = [int(r) for r in db.roots[:int(db.root_offsets[-1])]]
+    while stack:
+        n = stack.pop()
+        if n in seen:
+            continue
+        seen.add(n)
+        args = (int(a[n]), int(b[n]), int(c[n]))
+        for i in _REFS[int(op[n])]:
+            if args[i] != NONE and args[i] not in seen:
+                stack.append(args[i])
+    return np.asarray(sorted(seen), np.int64)
+
+
+def find_keccak_sites(db, syms, off: np.ndarray, bm: Optional[_BitMaps] = None):
+    """``(sites, skipped)``: the keccak sites of the batch (at most MAX_SITES, by ascending UF node)
+    and how many applications were left out, by reason."""
+    from .lower import SLICE, split_slice
+    if bm is None:
+        opaque = frozenset(v for v, (f, _) in syms.derived.items() if SLICE in f)
+        bm = _BitMaps(db.nodes, db.consts, opaque)
+    op, a, b = bm.op, bm.a, bm.b
+    reach = _reachable(db)
+    skipped: Dict[str, int] = {}
+
+    def skip(why: str) -> None:
+        skipped[why] = skipped.get(why, 0) + 1
+    # the intervals: Or(ULT(lo, u), EQ(lo, u)) / ULE(lo, u) and ULT(u, hi), lo and hi constant
+    los: Dict[int, int] = {}
+    his: Dict[int, int] = {}
+    for n in reach:
+        n = int(n)
+        o = int(op[n])
+        if o == _ULT and int(op[int(a[n])]) == _UF:
+            hi = bm.const_value(int(b[n]))
+            if hi is not None:
+                u = int(a[n])
+                his[u] = min(his.get(u, hi), hi)
+        elif o == _ULE and int(op[int(b[n])]) == _UF:
+            lo = bm.const_value(int(a[n]))
+            if lo is not None:
+                u = int(b[n])
+                los[u] = max(los.get(u, lo), lo)
+        elif o == _OR:
+            p, q = int(a[n]), int(b[n])
+            if int(op[p]) == _EQ:
+                p, q = q, p
+            if int(op[p]) == _ULT and int(op[q]) == _EQ and int(op[int(b[p])]) == _UF:
+                u, cn = int(b[p]), int(a[p])
+                lo = bm.const_value(cn)
+                if lo is not None and {int(a[q]), int(b[q])} == {u, cn}:
+                    los[u] = max(los.get(u, lo), lo)
+    derived_of: Dict[str, List[int]] = {}
+    for v, (fn, _) in syms.derived.items():
+        derived_of.setdefault(fn, []).append(v)
+    sites: List[KeccakSite] = []
+    for n in reach:
+        n = int(n)
+        o = int(op[n])
+        if o == _KECCAK_OP:
+            skip("interpreted")
+            continue
+        if o == _UF_WIDE and _KECCAK_NAME.match(syms.func_names[int(a[n])]):
+            skip("wide")
+            continue
+        if o != _UF or int(bm.c[n]) != NONE:
+            continue
+        f = int(a[n])
+        name = syms.func_names[f]
+        mt = _KECCAK_NAME.match(name)
+        if mt is None:
+            continue
+        nb = int(mt.group(1))
+        if nb % 32 or nb > MAX_SITE_BITS or nb != int(bm.w[int(b[n])]) or int(bm.w[n]) != 256:
+            skip("wide" if nb > MAX_SITE_BITS else "misaligned")
+            continue
+        inv = syms.funcs.get(name + "-1")
+        if inv is None:
+            skip("no_inverse")
+            continue
+        x = int(b[n])
+        segs = bm.map(x)
+        if segs is None:
+            under = _reachable(_OneRoot(db, x))
+            nested = any(int(op[int(m)]) in (_UF, _UF_CHUNK, _UF_WIDE, _KECCAK_OP) for m in under)
+            skip("nested" if nested else "unmapped")
+            continue
+        if bm.floors[x]:
+            skip("floor")
+            continue
+        pos, aligned = 0, True
+        for v, s, k in segs:
+            if pos % 32 or k % 32 or (v >= 0 and s % 32):
+                aligned = False
+            pos += k
+        if not aligned:
+            skip("misaligned")
+            continue
+        if n not in los or n not in his:
+            skip("no_interval")
+            continue
+        par = image_params(los[n], his[n])
+        if par is None:
+            skip("no_interval")
+            continue
+        inverses = [(inv, 0, nb)]
+        bad = False
+        for g, gname in enumerate(syms.func_names):
+            base_name, sl = split_slice(gname)
+            if sl is not None and base_name == name + "-1":
+                if sl[0] % 32 or (sl[1] - sl[0]) % 32 or sl[1] > nb:
+                    bad = True
+                inverses.append((g, sl[0], sl[1]))
+        if bad:
+            skip("misaligned")
+            continue
+        if any(derived_of.get(syms.func_names[g]) for g, _, _ in inverses):
+            skip("inverse_derived")
+            continue
+        dvs = sorted(derived_of.get(name, []))
+        if len(dvs) > MAX_COLLISIONS:
+            skip("too_many_derived")
+            continue
+        if len(sites) >= MAX_SITES:
+            skip("too_many_sites")
+            continue
+        words: List[Tuple[int, int]] = []
+        for v, s, k in segs:
+            for i in range(k // 32):
+                words.append((int(off[v]) + s // 32 + i, 0) if v >= 0 else (-1, (s >> (32 * i)) & 0xFFFFFFFF))
+        coll = [(int(syms.derived[v][1][0]), v, int(off[v])) for v in dvs]
+        sites.append(KeccakSite(n, f, nb, inverses, segs, words, par[0], par[1], coll))
+    return sites, skipped
+
+
+class _OneRoot:
+    """A one-root view of a DAG batch (:func:`_reachable` under a single node)."""
+
+    def __init__(self, db, root: int):
+        self.nodes = db.nodes
+        self.roots = np.asarray([root], np.uint32)
+        self.root_offsets = np.asarray([0, 1], np.int64)
+
+
+def keccak_sites_of(db, syms, off: np.ndarray, blocks: List[Tuple[Tuple, np.ndarray]]) -> KeccakSites:
+    """The batch's sites with each block's active mask: site i is active in block j iff the
+    block's patch assigns (a value or a floor of) a variable of the site's map."""
+    sites, skipped = find_keccak_sites(db, syms, off)
+    active = np.zeros(len(blocks), np.uint64)
+    for j, (patch, _) in enumerate(blocks):
+        vs = {el[0] for el in patch}
+        m = 0
+        for i, s in enumerate(sites):
+            if vs & s.vars:
+                m |= 1 << i
+        active[j] = m
+    return KeccakSites(sites, active, skipped)
+
+
+def _site_values(ks: KeccakSites, words: np.ndarray, n_lru: int, starts: np.ndarray):
+    """Per site ``(candidates k, x words [n, n/32], v words [n, 8])`` over the candidates of the
+    blocks the site is active in; ``words`` is the batch's row matrix (patched and floored)."""
+    out = []
+    for i, s in enumerate(ks.sites):
+        js = np.flatnonzero((ks.active >> np.uint64(i)) & np.uint64(1))
+        cols = np.concatenate([np.arange(int(starts[j]), int(starts[j + 1]), dtype=np.int64) for j in js]) \
+            if len(js) else np.zeros(0, np.int64)
+        nw = s.n_bits // 32
+        xw = np.zeros((len(cols), nw), np.uint32)
+        for l, (row, cv) in enumerate(s.words):
+            xw[:, l] = words[row, n_lru + cols] if row >= 0 else cv
+        raw = np.ascontiguousarray(xw[:, ::-1]).astype(">u4").tobytes()
+        xs = [int.from_bytes(raw[4 * nw * t:4 * nw * (t + 1)], "big") for t in range(len(cols))]
+        vs = keccak_images(xs, s.n_bits, s.base, s.b)
+        vw = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vs), "<u4").reshape(len(cols), 8).copy()
+        for key, _, r0 in s.collisions:
+            hit = np.flatnonzero((xw == np.asarray(to_words(key, s.n_bits), np.uint32)[None, :]).all(axis=1))
+            if len(hit):
+                vw[hit] = words[r0:r0 + 8, n_lru + cols[hit]].T
+        out.append((cols, xw, vw))
+    return out
+
+
 def _table_triples(lru: ModelBatch, blocks: List[Tuple[Tuple, np.ndarray]], syms):
     """Per function: (block, position among the block's changed derived vars of it, var) triples:
     the entries a block's patch adds in front of the base model's (per function by ascending
@@ -420,14 +690,20 @@ def _table_triples(lru: ModelBatch, blocks: List[Tuple[Tuple, np.ndarray]], syms
     return per_f
 
 
-def _function_tables(lru: ModelBatch, blocks, syms, per_f, src, starts, sizes, off, K, words, composed):
+def _function_tables(lru: ModelBatch, blocks, syms, per_f, src, starts, sizes, off, K, words, composed, sites=None,
+                     site_words=None):
     """The fully materialised function tables of the LRU models followed by the K candidates:
     ``(entry_ptr, entry_words, entry_base, else_words, else_base)``.  A candidate's table is its
     base model's entries, preceded by an entry for every derived variable of that function its
     block's patch changed (so table and derived column agree; first match wins).  ``words`` is the
     batch's row matrix, or None with ``composed`` (:func:`_compose_blocks`) to compute the added
-    values from the LRU rows and the blocks' composed patches."""
+    values from the LRU rows and the blocks' composed patches.  ``sites`` (:class:`KeccakSites`):
+    each active site's entries follow the base model's, read from ``site_words`` (default ``words``)."""
     n_lru = lru.n_models
+    site_cnt = site_vals = None
+    if sites is not None and sites.active.any() and K:   # (no active block: no entry, and no rows needed)
+        site_cnt = sites.site_counts(len(lru.funcs))
+        site_vals = _site_values(sites, words if site_words is None else site_words, n_lru, starts)
     M = n_lru + K
     F = len(lru.funcs)
     eptr = np.zeros((F, M + 1), np.int64)
@@ -446,7 +722,8 @@ def _function_tables(lru: ModelBatch, blocks, syms, per_f, src, starts, sizes, o
             add_cnt = np.repeat(np.bincount(tj, minlength=len(blocks)), sizes)
         else:
             add_cnt = np.zeros(K, np.int64)
-        counts = np.concatenate([base_cnt, cnt_gen + add_cnt])
+        site_add = np.repeat(site_cnt[f], sizes) if site_cnt is not None else np.zeros(K, np.int64)
+        counts = np.concatenate([base_cnt, cnt_gen + add_cnt + site_add])
         eptr[f, 1:] = np.cumsum(counts)
         ent = lru.entry_words[int(lru.entry_base[f]):int(lru.entry_base[f]) + int(base_ptr[-1]) * s].reshape(-1, s)
         out = np.zeros((int(eptr[f, -1]), s), np.uint32)
@@ -502,6 +779,20 @@ def _function_tables(lru: ModelBatch, blocks, syms, per_f, src, starts, sizes, o
                 dst = gstart[cand] + within
                 srcrow = base_ptr[src[cand]] + within
                 out[dst] = ent[srcrow]
+        if site_cnt is not None and site_add.any():
+            # the active sites' entries behind the base model's, in site order: x -> v in the
+            # site's own function, v -> bits [lo, hi) of x in its inverse and the inverse's slices
+            at = gstarts + add_cnt + cnt_gen
+            for i, sl in sites.contributions(f):
+                cols, xw, vw = site_vals[i]
+                if not len(cols):
+                    continue
+                rows = at[cols]
+                if sl is None:
+                    out[rows] = np.concatenate([xw, vw], axis=1)
+                else:
+                    out[rows] = np.concatenate([vw, xw[:, sl[0] // 32:sl[1] // 32]], axis=1)
+                at[cols] += 1
         ebase[f] = wpos
         ew_chunks.append(out.reshape(-1))
         wpos += out.size
@@ -527,7 +818,13 @@ class CandidateSet:
 
     derivation: Optional[Derivation] = None
     table_derivation: Optional[TableDerivation] = None   # (a generator with ``device_tables``)
+    keccak_sites: Optional[KeccakSites] = None           # (a generator with ``keccak_sites``)
     _row_args = None
+
+    @property
+    def keccak_skips(self) -> Dict[str, int]:
+        """keccak applications that are no site, counted by reason (empty without ``keccak_sites``)."""
+        return dict(self.keccak_sites.skipped) if self.keccak_sites is not None else {}
 
     def rows(self) -> np.ndarray:
         """The whole batch's variable rows [rows, n_lru + K] (:func:`_candidate_rows`; as
@@ -550,7 +847,7 @@ class CandidateSet:
                 return ModelBatch(b.var_widths, words)
             per_f = _table_triples(lru, blocks, self.syms)
             return ModelBatch(b.var_widths, words, b.funcs, *_function_tables(
-                lru, blocks, self.syms, per_f, src, starts, sizes, off, K, words, None), b.index_base)
+                lru, blocks, self.syms, per_f, src, starts, sizes, off, K, words, None, self.keccak_sites), b.index_base)
         return ModelBatch(b.var_widths, self.rows(), b.funcs, b.entry_ptr, b.entry_words, b.entry_base,
                           b.else_words, b.else_base, b.index_base)
 
@@ -605,16 +902,53 @@ class CandidateSet:
                 funcs[fname] = (e, els)
             else:
                 asg[name] = val
+        ks = self.keccak_sites
+        if ks is not None and ks.sites:
+            self._materialize_sites(ks, int(ks.active[int(self.block_of[k])]), asg, funcs, names)
         return Model(asg, funcs)
+
+    def _materialize_sites(self, ks: KeccakSites, mask: int, asg, funcs, names) -> None:
+        """The active sites' entries of one candidate, in site order, behind what the model holds
+        (``setdefault``: an entry for the same key keeps its value)."""
+        def value(v: int) -> int:
+            name, w = names[v]
+            if v in self.syms.derived:
+                fname, fargs = self.syms.derived[v]
+                interp = funcs.get(fname)
+                val = 0 if interp is None else int(interp[0].get(tuple(fargs), interp[1]))
+            else:
+                val = int(asg.get(name, 0) or 0)
+            return val & ((1 << max(w, 1)) - 1)
+        fnames = self.syms.func_names
+        for i, s in enumerate(ks.sites):
+            if not (mask >> i) & 1:
+                continue
+            x, pos = 0, 0
+            for v, lo, n in s.segs:
+                bits = lo if v < 0 else (value(v) >> lo) & ((1 << n) - 1)
+                x |= bits << pos
+                pos += n
+            hit = [var for key, var, _ in s.collisions if key == x]
+            img = value(hit[0]) if hit else keccak_images([x], s.n_bits, s.base, s.b)[0]
+            for fname, key, val in ((fnames[s.func], x, img), (fnames[s.inverses[0][0]], img, x)):
+                e, els = funcs.get(fname, ({}, 0))
+                e = dict(e)
+                e.setdefault((key,), val)
+                funcs[fname] = (e, els)
 
 
 class CandidateGenerator:
     """Generates up to ``max_candidates`` candidates for a batch of conjunctions (seeded)."""
 
     def __init__(self, max_candidates: int = 100_000, seed: int = 0, random_frac: float = 0.05, per_query: int = 16,
-                 fill: bool = False, device_rows: bool = False, device_tables: bool = False):
+                 fill: bool = False, device_rows: bool = False, device_tables: bool = False,
+                 keccak_sites: bool = False):
         if device_tables and not device_rows:
             raise ValueError("device_tables needs device_rows: the derived tables read the derived rows")
+        # candidates whose patch changes the input of a keccak256_<n> application get that input's
+        # image entered in keccak256_<n> and its inverse (KeccakSites; meant for device_tables: the
+        # host modes hash every (candidate, site) on the CPU)
+        self.keccak_sites = bool(keccak_sites)
         # the candidates' function tables are not materialised either: the set carries a
         # TableDerivation next to the Derivation (needs device_rows)
         self.device_tables = bool(device_tables)
@@ -744,10 +1078,13 @@ class CandidateGenerator:
                 break
             if not add(patch, bases, dedupe=False):
                 break
+        if self.keccak_sites:   # (the batch _serialize looks for keccak sites in; off: the call as it always was)
+            return self._serialize(lru_batch, blocks, syms, lru_models, db)
         return self._serialize(lru_batch, blocks, syms, lru_models)
 
     # ------------------------------------------------------------ serialization
-    def _serialize(self, lru: ModelBatch, blocks: List[Tuple[Tuple, np.ndarray]], syms, lru_models) -> CandidateSet:
+    def _serialize(self, lru: ModelBatch, blocks: List[Tuple[Tuple, np.ndarray]], syms, lru_models,
+                   db=None) -> CandidateSet:
         n_lru = lru.n_models
         sizes = np.asarray([len(b) for _, b in blocks], np.int64)
         K = int(sizes.sum())
@@ -766,9 +1103,14 @@ class CandidateGenerator:
             words = None
         else:
             words = _candidate_rows(lru, src, starts, sizes, blocks, syms, off, K)
+        # the batch's keccak sites (found once per batch) and the blocks' active masks
+        sites = None
+        if self.keccak_sites and db is not None and lru.funcs:
+            sites = keccak_sites_of(db, syms, off, blocks)
 
         def done(mb: ModelBatch) -> CandidateSet:
             cs = CandidateSet(mb, n_lru, base, block_of, [p for p, _ in blocks], syms, lru_models)
+            cs.keccak_sites = sites
             if deriv is not None:
                 cs.derivation = deriv
                 cs._row_args = (lru, src, starts, sizes, blocks, off, K)
@@ -782,5 +1124,10 @@ class CandidateGenerator:
             cs = done(ModelBatch(lru.var_widths, None, lru.funcs, n_models=M, tables=False))
             cs.table_derivation = table_derivation_arrays(lru, len(blocks), per_f, syms)
             return cs
-        eptr, ew, ebase, el, elb = _function_tables(lru, blocks, syms, per_f, src, starts, sizes, off, K, words, composed)
+        site_words = words
+        if sites is not None and sites.active.any() and words is None:
+            # (device_rows with host tables: the sites' inputs are read from the rows, built here for that)
+            site_words = _candidate_rows(lru, src, starts, sizes, blocks, syms, off, K)
+        eptr, ew, ebase, el, elb = _function_tables(lru, blocks, syms, per_f, src, starts, sizes, off, K, words, composed,
+                                                    sites, site_words)
         return done(ModelBatch(lru.var_widths, words, lru.funcs, eptr, ew, ebase, el, elb, 0, n_models=M))

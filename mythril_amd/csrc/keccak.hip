@@ -201,6 +201,97 @@ hipError_t launch_keccak_columns(const KcCol* cols, int n_cols, const KcMapEntry
   return hipGetLastError();
 }
 
+// Keccak sites of a derived upload (qs_launch.h launch_derive_keccak_sites): grid.y = site,
+// grid.x = 256-candidate blocks, a wave along the candidate axis, so the site's layout is uniform
+// and the input words are coalesced SoA row reads as in keccak_column_kernel.  Pairs whose block
+// does not activate the site exit on the block's mask (blocks are contiguous in k: normally the
+// whole wave).  The image v = base + ((D mod 2^b) << 6) is formed limb by limb with a plain carry
+// chain (b <= 192 and base + 64 * 2^b <= 2^256, checked on the host: nothing is shifted out and
+// the sum does not wrap).
+__global__ __launch_bounds__(256) void derive_keccak_sites_kernel(const KsSite* __restrict__ sites,
+                                                                  const KcMapEntry* __restrict__ words,
+                                                                  const KsColl* __restrict__ coll,
+                                                                  const uint32_t* __restrict__ keys,
+                                                                  const uint64_t* __restrict__ active, uint64_t live,
+                                                                  const int64_t* __restrict__ block_start, int n_blocks,
+                                                                  const uint32_t* __restrict__ vars,
+                                                                  const uint32_t* __restrict__ var_off, int64_t n_base,
+                                                                  int64_t K, uint32_t* __restrict__ v_out) {
+  const int si = blockIdx.y;
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= K) return;
+  const int j = derive_block_of(block_start, n_blocks, k);
+  if (!(((active[j] & live) >> si) & 1ull)) return;   // (live: the sites that have a slot in v_out)
+  const KsSite s = sites[si];
+  const int64_t M = n_base + K, m = n_base + k;
+  const KcMapEntry* e = words + s.map_off;
+  const uint32_t nw = s.n_words;
+  const uint32_t nblocks = (4u * nw) / 136u + 1u;
+  uint64_t A[25];
+#pragma unroll
+  for (int q = 0; q < 25; q++) A[q] = 0;
+#pragma unroll
+  for (int b = 0; b < 2; b++) {
+    if ((uint32_t)b >= nblocks) break;
+#pragma unroll
+    for (int p = 0; p < 34; p++) {
+      const uint32_t gi = 34u * b + p;
+      uint32_t w = 0;
+      if (gi < nw) {
+        // message word gi is the input's limb nw - 1 - gi (the message is x big-endian)
+        const KcMapEntry x = e[nw - 1u - gi];
+        w = __builtin_bswap32(x.row == ~0u ? x.value : vars[(int64_t)x.row * M + m]);
+      } else if (gi == nw) {
+        w = 0x01u;   // pad byte at message position 4 nw
+      }
+      A[p >> 1] ^= (uint64_t)w << (32 * (p & 1));
+    }
+    if ((uint32_t)b == nblocks - 1u) A[16] ^= 0x8000000000000000ull;
+    keccak_f(A);
+  }
+  uint32_t v[8];
+  uint32_t prev = 0;
+  uint64_t carry = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint64_t q = A[(7 - i) >> 1];
+    uint32_t d = __builtin_bswap32((uint32_t)(((7 - i) & 1) ? (q >> 32) : q));   // digest limb i
+    const uint32_t nb = s.b > 32u * i ? min(32u, s.b - 32u * i) : 0u;
+    d &= nb >= 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+    carry += (uint64_t)((d << 6) | (prev >> 26)) + (uint64_t)s.base[i];
+    v[i] = (uint32_t)carry;
+    carry >>= 32;
+    prev = d;
+  }
+  // collision rule: x equal to the constant key of a derived variable of the site's function
+  for (int c = 0; c < s.n_coll; c++) {
+    const KsColl cl = coll[s.coll_off + c];
+    bool same = true;
+    for (uint32_t l = 0; l < nw && same; l++) {
+      const KcMapEntry x = e[l];
+      same = (x.row == ~0u ? x.value : vars[(int64_t)x.row * M + m]) == keys[cl.key_off + l];
+    }
+    if (same) {
+      const int64_t r0 = var_off[cl.var];
+#pragma unroll
+      for (int i = 0; i < 8; i++) v[i] = vars[(r0 + i) * M + m];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) v_out[((int64_t)ks_slot(live, si) * 8 + i) * K + k] = v[i];   // (active: si is in live)
+}
+
+hipError_t launch_derive_keccak_sites(const KsSite* sites, int n_sites, const KcMapEntry* words, const KsColl* coll,
+                                      const uint32_t* keys, const uint64_t* active, uint64_t live, const int64_t* block_start,
+                                      int32_t n_blocks, const uint32_t* vars, const uint32_t* var_off, int64_t n_base,
+                                      int64_t K, uint32_t* v_out, hipStream_t st) {
+  if (n_sites <= 0 || K <= 0 || live == 0) return hipSuccess;   // (no site active anywhere: nothing to hash)
+  if (n_sites > 64 || n_blocks < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(derive_keccak_sites_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)n_sites), dim3(256), 0, st,
+                     sites, words, coll, keys, active, live, block_start, (int)n_blocks, vars, var_off, n_base, K, v_out);
+  return hipGetLastError();
+}
+
 hipError_t launch_keccak(const uint8_t* data, const int64_t* offsets, int n, uint8_t* out, hipStream_t st) {
   hipLaunchKernelGGL(keccak256_kernel, dim3((n + 63) / 64), dim3(64), 0, st, data, offsets, n, out);
   return hipGetLastError();

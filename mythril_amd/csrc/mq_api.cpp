@@ -377,6 +377,8 @@ struct mq_ctx {
   // ... and the tables the device writes, which no host data is staged into: buffers of their own,
   // kept across uploads like vars (entry_ptr / entry_words / else_words / dense_words view them)
   DevBuf dt_entry_ptr, dt_entry_words, dt_else, dt_dense;
+  // a keccak-derived upload's inputs (views into mpack) and the sites' images (a buffer of its own)
+  DevBuf ks_sites, ks_words, ks_inv, ks_coll, ks_keys, ks_active, ks_fmask, ks_cnt, ks_v;
   uint64_t table_uploads = 0;   // derived-table uploads taken
   std::vector<FuncDev> funcs_dev_h;   // host copy of `funcs` (mq_models_download_funcs)
   int64_t else_words_n = 0, dense_words_n = 0;
@@ -1010,11 +1012,18 @@ void mq_ctx_destroy(mq_ctx* c) {
 struct TableSizes {
   std::vector<int32_t> add_cnt;          // [F][n_blocks] additions of block j to function f
   std::vector<int64_t> total, emax;      // [F] entries over all models / the most in one model
+  // keccak sites (mq_models_upload_derived_keccak): the sites that append to function f, and the
+  // active ones among them per block
+  std::vector<uint64_t> site_fmask;      // [F]
+  std::vector<int32_t> site_cnt;         // [F][n_blocks]
 };
 static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* dv = nullptr,
-                      const mq_table_derivation* td = nullptr, const TableSizes* ts = nullptr) {
+                      const mq_table_derivation* td = nullptr, const TableSizes* ts = nullptr,
+                      const mq_keccak_derivation* ks = nullptr) {
   if (!c || !mb || mb->n_models < 0 || mb->n_vars < 0 || mb->n_funcs < 0) return MQ_ERR_ARG;
   if (mb->n_funcs == 0) td = nullptr;   // (no tables to derive)
+  if (!td || !ks || ks->n_sites == 0 || dv->n_derived == 0) ks = nullptr;   // (no site entries)
+  uint64_t ks_live = 0;   // sites active in some block
   if (mb->n_models > 0x7FFFFFFF || mb->index_base + mb->n_models > 0x7FFFFFFE) return MQ_ERR_ARG;
   HIPCHK(hipSetDevice(c->device));
   const int64_t M = mb->n_models;
@@ -1109,7 +1118,8 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   HIPCHK(c->vars.ensure(sizeof(uint32_t) * (size_t)(rows + 1) * M));
   for (DevBuf* b : {&c->dv_base, &c->dv_src, &c->dv_bstart, &c->dv_pptr, &c->dv_patches, &c->dv_fptr, &c->dv_floors,
                     &c->dt_bptr, &c->dt_bbase, &c->dt_bentries, &c->dt_belse, &c->dt_addptr, &c->dt_adds, &c->dt_addcnt,
-                    &c->dt_keys})
+                    &c->dt_keys, &c->ks_sites, &c->ks_words, &c->ks_inv, &c->ks_coll, &c->ks_keys, &c->ks_active,
+                    &c->ks_fmask, &c->ks_cnt})
     b->release();   // (views of the previous derived upload's block)
   if (dv) {
     // the base rows and the derivation tables ride in the staged block; the rows themselves are
@@ -1246,6 +1256,23 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
     HIPCHK(c->dt_entry_words.ensure(sizeof(uint32_t) * ((size_t)std::max<int64_t>(ew_total, 1) + kEntryPadWords)));
     HIPCHK(c->dt_else.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(else_n, 1)));
     HIPCHK(c->dt_dense.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(dense_n, 1)));
+    if (ks) {
+      const mq_keccak_word zw{~0u, 0};
+      const mq_keccak_collision zc{0, 0, 0};
+      const uint32_t zk = 0;
+      pk.add(c->ks_sites, ks->sites, (size_t)ks->n_sites);
+      pk.add(c->ks_words, ks->n_words > 0 ? ks->words : &zw, (size_t)std::max<int64_t>(ks->n_words, 1));
+      pk.add(c->ks_inv, ks->inverses, (size_t)std::max<int64_t>(ks->n_inverses, 0), 1);
+      pk.add(c->ks_coll, ks->n_collisions > 0 ? ks->collisions : &zc, (size_t)std::max<int64_t>(ks->n_collisions, 1));
+      pk.add(c->ks_keys, ks->n_key_words > 0 ? ks->key_words : &zk, (size_t)std::max<int64_t>(ks->n_key_words, 1));
+      pk.add(c->ks_active, ks->active, (size_t)nblk);
+      pk.add(c->ks_fmask, ts->site_fmask.data(), ts->site_fmask.size());
+      pk.add(c->ks_cnt, ts->site_cnt.data(), ts->site_cnt.size(), 1);
+      // the image scratch holds a slot only for the sites some block activates (64 sites x 10^5
+      // candidates would be 205 MB; a batch's patches reach a few of them)
+      for (int64_t j = 0; j < nblk; j++) ks_live |= ks->active[j];
+      HIPCHK(c->ks_v.ensure(sizeof(uint32_t) * 8 * (size_t)std::max(__builtin_popcountll(ks_live), 1) * (size_t)dv->n_derived));
+    }
   } else if (F > 0) {
     pk.add(c->entry_ptr, mb->entry_ptr, (size_t)F * (M + 1));
     // (padded: G's table scan reads the first word of up to 7 entries past a model's last one,
@@ -1304,6 +1331,21 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
     a.K = dv->n_derived;
     a.n_blocks = dv->n_blocks;
     a.n_funcs = F;
+    if (ks) {
+      // the sites' images first (from the masked rows); the entry kernels read them
+      a.n_sites = ks->n_sites;
+      a.ks_sites = c->ks_sites.as<KsSite>();
+      a.ks_words = c->ks_words.as<KcMapEntry>();
+      a.ks_inv = c->ks_inv.as<KsInv>();
+      a.ks_active = c->ks_active.as<uint64_t>();
+      a.ks_fmask = c->ks_fmask.as<uint64_t>();
+      a.ks_cnt = c->ks_cnt.as<int32_t>();
+      a.ks_v = c->ks_v.as<uint32_t>();
+      a.ks_union = ks_live;
+      HIPCHK(launch_derive_keccak_sites(a.ks_sites, a.n_sites, a.ks_words, c->ks_coll.as<KsColl>(), c->ks_keys.as<uint32_t>(),
+                                        a.ks_active, ks_live, a.block_start, a.n_blocks, a.vars, a.var_off, a.n_base, a.K,
+                                        c->ks_v.as<uint32_t>(), c->stream));
+    }
     HIPCHK(launch_derive_tables(a, max_words, dense_n > 0, c->stream));
     c->table_uploads++;
   }
@@ -1484,7 +1526,8 @@ int mq_table_derivation_check(const mq_model_batch* mb, const mq_derivation* d, 
 
 // Per function the total entry count and the largest per-model count of the derived tables, from
 // the base counts, src and the per-block addition counts: O(F * (K + additions)) integer adds.
-static void derived_table_sizes(const mq_model_batch* mb, const mq_derivation* d, const mq_table_derivation* t, TableSizes& s) {
+static void derived_table_sizes(const mq_model_batch* mb, const mq_derivation* d, const mq_table_derivation* t, TableSizes& s,
+                                const mq_keccak_derivation* ks = nullptr) {
   const int F = mb->n_funcs;
   const int64_t nb = d->n_base, nblk = d->n_blocks;
   s.add_cnt.assign((size_t)F * (size_t)nblk, 0);
@@ -1492,12 +1535,25 @@ static void derived_table_sizes(const mq_model_batch* mb, const mq_derivation* d
   s.emax.assign((size_t)F, 0);
   for (int64_t j = 0; j < nblk; j++)
     for (int64_t q = t->add_ptr[j]; q < t->add_ptr[j + 1]; q++) s.add_cnt[(size_t)t->adds[q].func * nblk + j]++;
+  if (ks && ks->n_sites > 0) {
+    // the active sites' entries per (function, block): O(F * blocks) popcounts
+    s.site_fmask.assign((size_t)std::max(F, 1), 0);
+    s.site_cnt.assign((size_t)F * (size_t)nblk, 0);
+    for (int i = 0; i < ks->n_sites; i++) {
+      const mq_keccak_site& x = ks->sites[i];
+      s.site_fmask[x.func] |= 1ull << i;
+      for (int q = 0; q < x.n_inv; q++) s.site_fmask[ks->inverses[x.inv_off + q].func] |= 1ull << i;
+    }
+    for (int f = 0; f < F; f++)
+      for (int64_t j = 0; j < nblk; j++)
+        s.site_cnt[(size_t)f * nblk + j] = __builtin_popcountll(ks->active[j] & s.site_fmask[f]);
+  }
   for (int f = 0; f < F; f++) {
     const int64_t* p = t->base->entry_ptr + (int64_t)f * (nb + 1);
     int64_t total = p[nb] - p[0], emax = 0;
     for (int64_t m = 0; m < nb; m++) emax = std::max(emax, p[m + 1] - p[m]);
     for (int64_t j = 0; j < nblk; j++) {
-      const int64_t add = s.add_cnt[(size_t)f * nblk + j];
+      const int64_t add = s.add_cnt[(size_t)f * nblk + j] + (s.site_cnt.empty() ? 0 : s.site_cnt[(size_t)f * nblk + j]);
       for (int64_t k = d->block_start[j]; k < d->block_start[j + 1]; k++) {
         const int64_t n = add + (d->src[k] >= 0 ? p[d->src[k] + 1] - p[d->src[k]] : 0);
         total += n;
@@ -1521,6 +1577,88 @@ int mq_models_upload_derived_tables(mq_ctx* c, const mq_model_batch* mb, const m
   c->shard_lo.assign(1, 0);
   c->M_total = mb->n_models;
   return upload_one(c, mb, d, t, &ts);
+}
+
+static_assert(sizeof(mq_keccak_site) == sizeof(KsSite) && sizeof(mq_keccak_site) == 72 && sizeof(mq_keccak_word) == sizeof(KcMapEntry) &&
+                  sizeof(mq_keccak_inverse) == sizeof(KsInv) && sizeof(mq_keccak_collision) == sizeof(KsColl) &&
+                  sizeof(mq_keccak_collision) == 16,
+              "the keccak derivation goes to the device as it is");
+
+int mq_keccak_derivation_check(const mq_model_batch* mb, const mq_derivation* d, const mq_keccak_derivation* s) {
+  if (!mb || !d || !s || mb->n_vars < 0 || mb->n_funcs < 0 || d->n_blocks < 0) return MQ_ERR_ARG;
+  if ((mb->n_vars > 0 && !mb->var_width) || (mb->n_funcs > 0 && !mb->funcs)) return MQ_ERR_ARG;
+  if (s->n_sites < 0 || s->n_sites > 64) return MQ_ERR_ARG;
+  if (s->n_sites == 0) return MQ_OK;
+  if (!s->sites || s->n_words < 0 || s->n_inverses < 0 || s->n_collisions < 0 || s->n_key_words < 0) return MQ_ERR_ARG;
+  if ((s->n_words > 0 && !s->words) || (s->n_inverses > 0 && !s->inverses) || (s->n_collisions > 0 && !s->collisions) ||
+      (s->n_key_words > 0 && !s->key_words) || (d->n_blocks > 0 && !s->active))
+    return MQ_ERR_ARG;
+  int64_t rows = 0;
+  for (int v = 0; v < mb->n_vars; v++) rows += nl_of(mb->var_width[v]);
+  const int F = mb->n_funcs;
+  for (int i = 0; i < s->n_sites; i++) {
+    const mq_keccak_site& x = s->sites[i];
+    // the function and its inverses, and their widths
+    if (x.func < 0 || x.func >= F || x.n_words < 1 || x.n_words > 64) return MQ_ERR_ARG;
+    const mq_func_desc& fx = mb->funcs[x.func];
+    if (fx.arity != 1 || fx.arg_width[0] != 32u * x.n_words || fx.result_width != 256) return MQ_ERR_ARG;
+    if (x.inv_off < 0 || x.n_inv < 0 || (int64_t)x.inv_off + x.n_inv > s->n_inverses) return MQ_ERR_ARG;
+    for (int q = 0; q < x.n_inv; q++) {
+      const mq_keccak_inverse& iv = s->inverses[x.inv_off + q];
+      if (iv.func < 0 || iv.func >= F || iv.func == x.func) return MQ_ERR_ARG;
+      const mq_func_desc& fi = mb->funcs[iv.func];
+      if (fi.arity != 1 || fi.arg_width[0] != 256 || fi.result_width == 0 || fi.result_width % 32) return MQ_ERR_ARG;
+      if ((int64_t)iv.lo_word + fi.result_width / 32 > (int64_t)x.n_words) return MQ_ERR_ARG;
+      for (int r = 0; r < q; r++)
+        if (s->inverses[x.inv_off + r].func == iv.func) return MQ_ERR_ARG;
+    }
+    // the word map
+    if (x.map_off < 0 || x.map_off + (int64_t)x.n_words > s->n_words) return MQ_ERR_ARG;
+    for (uint32_t l = 0; l < x.n_words; l++) {
+      const mq_keccak_word& w = s->words[x.map_off + l];
+      if (w.row != ~0u && (int64_t)w.row >= rows) return MQ_ERR_ARG;
+    }
+    // the image: b <= 192, base a multiple of 64, base + 64 * 2^b <= 2^256
+    if (x.b > 192 || (x.base[0] & 63u)) return MQ_ERR_ARG;
+    {
+      uint64_t carry = 0;
+      uint32_t nonzero = 0;
+      for (int l = 0; l < 8; l++) {
+        const uint32_t bit = (x.b + 6) / 32 == (uint32_t)l ? 1u << ((x.b + 6) % 32) : 0u;
+        carry += (uint64_t)x.base[l] + bit;
+        nonzero |= (uint32_t)carry;
+        carry >>= 32;
+      }
+      // (a carry out of limb 7 over an all-zero sum is exactly 2^256: allowed)
+      if (carry && nonzero) return MQ_ERR_ARG;
+    }
+    // the collisions
+    if (x.coll_off < 0 || x.n_coll < 0 || x.n_coll > 8 || (int64_t)x.coll_off + x.n_coll > s->n_collisions) return MQ_ERR_ARG;
+    for (int q = 0; q < x.n_coll; q++) {
+      const mq_keccak_collision& cl = s->collisions[x.coll_off + q];
+      if (cl.var < 0 || cl.var >= mb->n_vars || mb->var_width[cl.var] != 256) return MQ_ERR_ARG;
+      if (cl.key_off < 0 || cl.key_off > s->n_key_words - (int64_t)x.n_words) return MQ_ERR_ARG;
+    }
+  }
+  // a block's mask names existing sites only
+  const uint64_t known = s->n_sites == 64 ? ~0ull : (1ull << s->n_sites) - 1ull;
+  for (int64_t j = 0; j < d->n_blocks; j++)
+    if (s->active[j] & ~known) return MQ_ERR_ARG;
+  return MQ_OK;
+}
+
+int mq_models_upload_derived_keccak(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* d,
+                                    const mq_table_derivation* t, const mq_keccak_derivation* s) {
+  // (host checks first: a malformed call answers before any device call)
+  if (mq_table_derivation_check(mb, d, t) != MQ_OK || mq_keccak_derivation_check(mb, d, s) != MQ_OK) return MQ_ERR_ARG;
+  if (!c || !c->peers.empty()) return MQ_ERR_ARG;
+  PhaseTimer pt(&c->host_t[8]);
+  TableSizes ts;
+  derived_table_sizes(mb, d, t, ts, s);
+  note_batch(c, mb, &ts.emax);
+  c->shard_lo.assign(1, 0);
+  c->M_total = mb->n_models;
+  return upload_one(c, mb, d, t, &ts, s);
 }
 
 int mq_models_funcs_sizes(mq_ctx* c, int64_t sizes[4]) {

@@ -1049,15 +1049,6 @@ hipError_t launch_pack_bool(const uint32_t* vars, uint64_t* masks, const uint32_
 // The base matrix (<= 100 models in the product path) is left to L2.
 static constexpr int kDeriveRowChunk = 16;
 
-__device__ __forceinline__ int derive_block_of(const int64_t* block_start, int n_blocks, int64_t k) {
-  int lo = 0, hi = n_blocks;   // the last block whose start is <= k (empty blocks before it are skipped)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (block_start[mid] <= k) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void derive_rows_kernel(uint32_t* vars, const uint32_t* base, const int32_t* src,
                                                           const int64_t* block_start, const int64_t* patch_ptr,
                                                           const RowPatch* patches, int64_t n_base, int64_t K,
@@ -1136,14 +1127,36 @@ hipError_t launch_derive_rows(uint32_t* vars, const uint32_t* base, const int32_
 // Derived function tables (qs_launch.h TableDerive).  Four kernels on one stream, each reading
 // what the one before wrote: row pointers (count + scan), entry words, else values, dense slots.
 
-// entries of function f in model m: a base model's own, or its source's plus its block's additions
+// entries of function f in model m: a base model's own, or its block's additions, its source's and
+// (a keccak-derived upload) one per active keccak site of the block that appends to f, in that order
 __device__ __forceinline__ int64_t table_count(const TableDerive& a, int f, int64_t m) {
   const int64_t* bp = a.b_ptr + (int64_t)f * (a.n_base + 1);
   if (m < a.n_base) return bp[m + 1] - bp[m];
   const int64_t k = m - a.n_base;
   const int32_t s = a.src[k];
   const int j = derive_block_of(a.block_start, a.n_blocks, k);
-  return (s >= 0 ? bp[s + 1] - bp[s] : 0) + (int64_t)a.add_cnt[(int64_t)f * a.n_blocks + j];
+  return (s >= 0 ? bp[s + 1] - bp[s] : 0) + (int64_t)a.add_cnt[(int64_t)f * a.n_blocks + j] +
+         (a.n_sites ? (int64_t)a.ks_cnt[(int64_t)f * a.n_blocks + j] : 0);
+}
+
+// Word i of the entry that keccak site `si` appends to function f in derived model k: x -> v in the
+// site's own function, v -> the limbs of x from lo_word in an inverse.  x is gathered from the
+// resident rows through the site's word map, v was written by derive_keccak_sites_kernel.
+__device__ __forceinline__ uint32_t site_entry_word(const TableDerive& a, int si, int f, int64_t k, int64_t i) {
+  const KsSite s = a.ks_sites[si];
+  const int64_t M = a.n_base + a.K;
+  int64_t xl;   // limb of x, or -1 - limb of v
+  if (s.func == f) {
+    xl = i < (int64_t)s.n_words ? i : -1 - (i - (int64_t)s.n_words);
+  } else {
+    uint32_t lo = 0;
+    for (int q = 0; q < s.n_inv; q++)
+      if (a.ks_inv[s.inv_off + q].func == f) lo = a.ks_inv[s.inv_off + q].lo_word;
+    xl = i < 8 ? -1 - i : (int64_t)lo + (i - 8);
+  }
+  if (xl < 0) return a.ks_v[((size_t)ks_slot(a.ks_union, si) * 8 + (size_t)(-1 - xl)) * (size_t)a.K + (size_t)k];
+  const KcMapEntry e = a.ks_words[s.map_off + xl];
+  return e.row == ~0u ? e.value : a.vars[(size_t)e.row * (size_t)M + (size_t)(a.n_base + k)];
 }
 
 // One workgroup per function: exclusive scan of the per-model entry counts into the function's
@@ -1218,7 +1231,15 @@ __global__ __launch_bounds__(256) void derive_table_entries_kernel(TableDerive a
         continue;
       }
       local -= na;
-      s = a.src[k];   // (>= 0: a model without a source has no entries past its additions)
+      s = a.src[k];   // (>= 0, or past the base entries: a model without a source has none)
+      const int64_t nbase = s >= 0 ? bp[s + 1] - bp[s] : 0;
+      if (a.n_sites && local >= nbase) {
+        // the (local - nbase)-th of the block's active sites that append to this function
+        uint64_t live = a.ks_active[j] & a.ks_fmask[f];
+        for (int64_t t = local - nbase; t > 0; t--) live &= live - 1;
+        out[w] = live ? site_entry_word(a, __builtin_ctzll(live), f, k, i) : 0u;
+        continue;
+      }
     }
     out[w] = bent[(bp[s] + local) * stride + i];
   }

@@ -142,7 +142,8 @@ hipError_t launch_derive_rows(uint32_t* vars, const uint32_t* base, const int32_
 // base models' tables and each block's additions, after the rows are derived and masked (an added
 // entry's value is the model's resident limbs of a variable).  Model m < n_base keeps base model
 // m's entries; derived model k of block j has the block's additions for the function first, in
-// list order, then the entries of base model src[k] (none for -1; else value 0).
+// list order, then the entries of base model src[k] (none for -1; else value 0), then (n_sites > 0)
+// one entry per active keccak site of the block that appends to the function, in site order.
 struct TableAdd {   // mq.h's mq_table_add
   int32_t func, var;
   int64_t key_off;
@@ -167,7 +168,55 @@ struct TableDerive {
   uint32_t* dense_words;         // zeroed by the caller
   int64_t n_base, K;
   int32_t n_blocks, n_funcs;
+  // keccak sites (mq_models_upload_derived_keccak; n_sites == 0: none, the pointers unused): a
+  // derived model's third segment, behind its base model's entries
+  int32_t n_sites;
+  const struct KsSite* ks_sites;
+  const struct KcMapEntry* ks_words;   // a site's input limbs: a row, or row == ~0u: the constant `value`
+  const struct KsInv* ks_inv;
+  const uint64_t* ks_active;     // [n_blocks] sites active in a block
+  const uint64_t* ks_fmask;      // [n_funcs] sites that append an entry to function f
+  const int32_t* ks_cnt;         // [n_funcs][n_blocks]: popcount(ks_active[j] & ks_fmask[f])
+  const uint32_t* ks_v;          // the sites' images, SoA [slot][limb 0..7][K] (derive_keccak_sites_kernel)
+  uint64_t ks_union;             // sites active in some block: only those have a slot in ks_v (ks_slot)
 };
+// slot of site `si` in the image scratch: its rank among the sites that are active in some block
+__device__ __forceinline__ int ks_slot(uint64_t ks_union, int si) { return __popcll(ks_union & ((1ull << si) - 1ull)); }
+// mq.h's mq_keccak_site / mq_keccak_inverse / mq_keccak_collision (mq_keccak_word is KcMapEntry)
+struct KsSite {
+  int32_t func;
+  uint32_t n_words;
+  int64_t map_off;
+  int32_t inv_off, n_inv;
+  int32_t coll_off, n_coll;
+  uint32_t b, pad;
+  uint32_t base[8];
+};
+struct KsInv {
+  int32_t func;
+  uint32_t lo_word;
+};
+struct KsColl {
+  int32_t var, pad;
+  int64_t key_off;
+};
+// One thread per (derived model, site), after the rows are derived, floored and masked: v of every
+// active pair into v_out[(ks_slot(live, site) * 8 + limb) * K + k], `live` the union of the blocks'
+// masks, v_out 8 * popcount(live) * K words (inactive pairs are left unwritten, never read)
+hipError_t launch_derive_keccak_sites(const KsSite* sites, int n_sites, const struct KcMapEntry* words, const KsColl* coll,
+                                      const uint32_t* keys, const uint64_t* active, uint64_t live, const int64_t* block_start,
+                                      int32_t n_blocks, const uint32_t* vars, const uint32_t* var_off, int64_t n_base,
+                                      int64_t K, uint32_t* v_out, hipStream_t st);
+
+// the last block whose start is <= k (empty blocks before it are skipped)
+__device__ __forceinline__ int derive_block_of(const int64_t* block_start, int n_blocks, int64_t k) {
+  int lo = 0, hi = n_blocks;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (block_start[mid] <= k) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 // threads of the one workgroup per function that scans the entry counts into entry_ptr: thread t
 // owns models [t * chunk, (t + 1) * chunk), chunk = ceil(M / kTableScanThreads)
 constexpr int kTableScanThreads = 256;

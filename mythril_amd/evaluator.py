@@ -15,8 +15,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ._abi import (MqDagBatch, MqDerivation, MqModelBatch, MqNode, MqStats, MqTableDerivation, MqTapeBatch, as_dag_batch,
-                   as_derivation, as_model_batch, as_table_derivation, as_tape_batch)
+from ._abi import (MqDagBatch, MqDerivation, MqKeccakDerivation, MqModelBatch, MqNode, MqStats, MqTableDerivation, MqTapeBatch,
+                   as_dag_batch, as_derivation, as_keccak_derivation, as_model_batch, as_table_derivation, as_tape_batch)
 from .models import ModelBatch
 from .tape import TapeBatch
 
@@ -99,6 +99,9 @@ def load_library(path: str = LIB_PATH):
         L.mq_table_derivation_check.argtypes = [C.POINTER(MqModelBatch), C.POINTER(MqDerivation), C.POINTER(MqTableDerivation)]
         L.mq_models_upload_derived_tables.argtypes = [P, C.POINTER(MqModelBatch), C.POINTER(MqDerivation),
                                                       C.POINTER(MqTableDerivation)]
+        L.mq_keccak_derivation_check.argtypes = [C.POINTER(MqModelBatch), C.POINTER(MqDerivation), C.POINTER(MqKeccakDerivation)]
+        L.mq_models_upload_derived_keccak.argtypes = [P, C.POINTER(MqModelBatch), C.POINTER(MqDerivation),
+                                                      C.POINTER(MqTableDerivation), C.POINTER(MqKeccakDerivation)]
         L.mq_models_funcs_sizes.argtypes = [P, C.POINTER(C.c_int64)]
         L.mq_models_download_funcs.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -428,17 +431,28 @@ class Evaluator:
 
     table_uploads = 0   # uploads that took the derived-table path (upload_models_derived with tables)
 
-    def upload_models_derived(self, mb: ModelBatch, derivation, tables=None) -> None:
+    keccak_uploads = 0   # uploads that derived keccak sites' entries (upload_models_derived with sites)
+
+    def upload_models_derived(self, mb: ModelBatch, derivation, tables=None, sites=None) -> None:
         """Replace the candidate set with ``derivation``'s base models followed by its derived
         ones, their variable rows expanded on the device (``mq_models_upload_derived``).  ``mb``
         describes all of them as for :meth:`upload_models`; its ``var_words`` may be absent.
         With ``tables`` (a :class:`mythril_amd.candidates.TableDerivation`) the function tables are
         derived on the device as well (``mq_models_upload_derived_tables``) and ``mb`` needs no
-        per-model array at all.  Single-device evaluators only."""
+        per-model array at all; with ``sites`` too (a :class:`mythril_amd.candidates.KeccakSites`)
+        the active keccak sites' entries are derived with them (``mq_models_upload_derived_keccak``;
+        without ``tables`` the host built those entries into ``mb``).  Single-device evaluators only."""
         s, keep = as_model_batch(mb)
         d, keep_d = as_derivation(derivation)
         self.upload_seq += 1
-        if tables is not None:
+        if tables is not None and sites is not None and sites.sites:
+            t, keep_t = as_table_derivation(tables)
+            k, keep_k = as_keccak_derivation(sites)
+            _check(self.lib.mq_models_upload_derived_keccak(self.ctx, C.byref(s), C.byref(d), C.byref(t), C.byref(k)),
+                   "mq_models_upload_derived_keccak")
+            self.table_uploads += 1
+            self.keccak_uploads += 1
+        elif tables is not None:
             t, keep_t = as_table_derivation(tables)
             _check(self.lib.mq_models_upload_derived_tables(self.ctx, C.byref(s), C.byref(d), C.byref(t)),
                    "mq_models_upload_derived_tables")

@@ -444,7 +444,7 @@ class VerdictEngine:
         elif len(getattr(self.evaluator, "devices", (0,))) == 1:
             # generator.device_rows: the device expands the candidates' rows from the LRU's
             # (device_tables: the function tables too, from the LRU's and the blocks' additions)
-            fh, t3, t4 = self._first_hit(db, cs.batch, cs.derivation, cs.table_derivation)
+            fh, t3, t4 = self._first_hit(db, cs.batch, cs.derivation, cs.table_derivation, getattr(cs, "keccak_sites", None))
         else:
             mb = cs.host_batch()   # (a multi-device context shards host rows)
             t2 = clock()
@@ -459,12 +459,14 @@ class VerdictEngine:
         fh = np.where(ok, fh, -2)
         return fh, cs
 
-    def _first_hit(self, tb, mb, derivation=None, tables=None):
+    def _first_hit(self, tb, mb, derivation=None, tables=None, sites=None):
         """Upload + compile + first-hit launch; returns (first hits, time after upload, time
         after compile)."""
         clock = time.perf_counter
         ev = self.evaluator
-        if derivation is not None:
+        if derivation is not None and sites is not None:
+            ev.upload_models_derived(mb, derivation, tables, sites)
+        elif derivation is not None:
             ev.upload_models_derived(mb, derivation, tables)
         else:
             ev.upload_models(mb)
@@ -772,8 +774,11 @@ class ModelCache:
         # MQ_DEVICE_CANDIDATES (opt-in): 1 = the candidates' rows are derived on the device,
         # 2 = their function tables as well
         mode = os.environ.get("MQ_DEVICE_CANDIDATES")
+        # MQ_CANDIDATE_KECCAK=1 (opt-in, meant for MQ_DEVICE_CANDIDATES=2): candidates whose patch
+        # changes a keccak256_<n> input get its image entered in the keccak tables (KeccakSites)
+        opts = {"keccak_sites": True} if os.environ.get("MQ_CANDIDATE_KECCAK") == "1" else {}
         gen = CandidateGenerator(args.quick_sat_candidate_budget, seed=len(self.stats) + self.stats["queries"],
-                                 device_rows=mode in ("1", "2"), device_tables=mode == "2")
+                                 device_rows=mode in ("1", "2"), device_tables=mode == "2", **opts)
         fh, cs = self.engine.candidate_first_hits([exprs[i] for i in todo], order, gen)
         for i, h in zip(todo, fh):
             if h < 0:

@@ -883,3 +883,50 @@ def merge_workload(n_queries: int, n_models: int, seed: int = 31):
                                int(rng.integers(0, 3)) * 35)
         records.append(Model(asg, funcs))
     return exprs, records
+
+
+TOKEN_SLOT = 1             # the mapping's storage slot (balances at slot 1)
+TOKEN_STORAGE_ELSE = 7     # every untouched balance: above the forks' `balance > 5`
+
+
+def token_fork_workload(n: int, n_models: int, seed: int = 41):
+    """Forks whose new conjunct compares a MAPPING KEY variable (``balances[msg.sender]``-shaped
+    paths): query q is ``And(key == C_q, UGT(Storage[keccak256_<w>(input)], 5), axioms)`` with
+    ``C_q`` a value no cached model holds, alternating between ``keccak256_512(Concat(sender, slot))``
+    (key = sender) and ``keccak256_256(owner)`` (key = owner), over one KeccakFunctionManager's
+    axioms for both inputs (function_managers.py create_conditions).  The ``n_models`` cached models
+    have other keys and keccak tables consistent with the axioms: images inside the manager's
+    intervals, inverses entered, else values 0; ``Storage`` holds 100 at each model's own images
+    and TOKEN_STORAGE_ELSE elsewhere.  A cached model misses every query on ``key == C_q``; the
+    model with the key patched and the new input's image entered in both keccak tables satisfies it.
+
+    Returns ``(exprs, records, manager)`` (records MRU first)."""
+    from .candidates import image_params, keccak_images
+    from .function_managers import KeccakFunctionManager
+    from .smt_model import Model
+    rng = np.random.Generator(np.random.PCG64(seed))
+    kfm = KeccakFunctionManager()
+    sender, owner = S.BitVecSym("sender_1", 256), S.BitVecSym("owner_1", 256)
+    storage = S.Array("Storage_0", 256, 256)
+    x512 = S.Concat(sender, S.BitVecVal(TOKEN_SLOT, 256))
+    h512, h256 = kfm.create_keccak(x512), kfm.create_keccak(owner)
+    axioms = kfm.create_conditions()
+    par = {w: image_params(*kfm.interval(w)) for w in (512, 256)}
+
+    def fresh() -> int:
+        return int.from_bytes(rng.bytes(20), "big") | (1 << 159)
+    records = []
+    for _ in range(n_models):
+        a, o = fresh(), fresh()
+        k512 = (a << 256) | TOKEN_SLOT
+        v512 = keccak_images([k512], 512, *par[512])[0]
+        v256 = keccak_images([o], 256, *par[256])[0]
+        records.append(Model({"sender_1": a, "owner_1": o},
+                             {"keccak256_512": ({(k512,): v512}, 0), "keccak256_512-1": ({(v512,): k512}, 0),
+                              "keccak256_256": ({(o,): v256}, 0), "keccak256_256-1": ({(v256,): o}, 0),
+                              "Storage_0": ({(v512,): 100, (v256,): 100}, TOKEN_STORAGE_ELSE)}))
+    exprs = []
+    for q in range(n):
+        key, h = ((sender, h512), (owner, h256))[q % 2]
+        exprs.append(S.And(key == S.BitVecVal(fresh(), 256), S.UGT(storage[h], S.BitVecVal(5, 256)), axioms))
+    return exprs, records, kfm
