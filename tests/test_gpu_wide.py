@@ -151,9 +151,10 @@ def test_address_key_mapping_uses_keccak_columns(evaluator):
 
 @pytest.mark.parametrize("seed", range(3))
 def test_wide_key_chunk_lookups_match_oracle(evaluator, seed):
-    """keccak256_4096 / _2560 keys matched 256 bits at a time (G_UFK0 / G_UFK / G_UFKV on the
-    assembly interpreter, h_ufk / h_ufkv on the C++ one): verdicts equal the oracle's and the
-    independent term evaluator's (tests/test_wide_keys.py)."""
+    """keccak256_4096 / _2560 keys matched 256 bits at a time (the stack program's G_UFK0 / G_UFK /
+    G_UFKV, which run as h_ufk / h_ufkv on the HIP C++ interpreter: the assembly interpreters have no
+    handler for them): verdicts equal the oracle's and the independent term evaluator's
+    (tests/test_wide_keys.py)."""
     import random
     import term_eval
     from test_wide_keys import _wide_cases
