@@ -204,7 +204,9 @@ typedef struct mq_stats {
   double node_evals;       /* sum over evaluated (= decided) (tape, model) pairs of |tape| nodes,
                               whether or not a wave left the tape early at a bail point */
   double alg_ops;          /* algorithmic 32-bit VALU ops (SURVEY §8(d) cost table) executed:
-                              ops a wave skipped at a bail point are not counted */
+                              ops a wave skipped at a bail point are not counted (bail points:
+                              tapes over the first eight variables; with MQ_G_BAIL=1 in the
+                              environment, read per upload, every conjunction tape) */
   int64_t pairs_evaluated; /* (tape, model) pairs actually evaluated (early exit skips the rest) */
   int32_t n_hits;
   int32_t n_unsupported;
@@ -581,7 +583,8 @@ int mq_tape_program(const mq_tape_batch* batch, int32_t t, uint32_t* words, int3
 
 /* Host-only: tape t compiled as a verdict tape for the G assembly interpreter's stack (what an
    upload builds for it: bail points and all, unlike mq_tape_compile_info_g, which reports the
-   column-program compile): the program G would run -- the spilled variant when the plain program
+   column-program compile; a tape that reads a variable past the first eight carries bail points
+   only under MQ_G_BAIL=1, the opt-in that also makes G take them): the program G would run -- the spilled variant when the plain program
    needs more than kQsaStackG slots, else the plain one -- into words[cap], *n_words its length (also
    when cap is too small, then nothing is copied), *depth_g / *n_temps_g its stack slots and LDS
    temps, *spilled whether it is the spilled variant (each may be NULL).  Returns 0, MQ_ERR_ARG,

@@ -16,6 +16,7 @@ Two variants are generated from the same handler code (one asm statement each, l
   G ("general", qsg_kernel):  variables pushed from the model rows in HBM (PUSH_MEM: the loads
      are issued by the push and waited for by the first consumer) or from rows staged in LDS;
      table-lookup subroutine (UF1).  EVM-shaped batches and hoisted column programs (mode 3).
+     Its BAIL handler (bail points of conjunction tapes, opt-in: MQ_G_BAIL=1) is the last one.
      The product G is the compact layout (NVG = 0, set_layout): no preloaded variables, 96 VGPRs
      so 5 waves per SIMD hide the push latency (profiles/r03u: C3 26.6 -> 23.8 ms, C4 6.0 ->
      5.8 ms, C5 69.1 -> 70.4 ms against the NVG = 4 layout, 128 VGPRs with the 4 variables the
@@ -1629,6 +1630,32 @@ def make_handlers(variant, pfx):
             hs.append(((kind + suf,) + tuple(key[1:]), pre + fused + (prof_point(kind + suf) if G else []) + (NEXT_G if G else NEXT_P)))
             if waits:
                 hs.append(((kind + suf + "_L",) + tuple(key[1:]), [LGKMWAIT] + fused + prof_point(kind + suf + "_L") + NEXT_G))
+    if G:
+        # bail point of a conjunction spine on G (MQ_G_BAIL=1; mq_api.cpp qsa_translate emits it
+        # only where no PUSH_MEM load is outstanding, never in column programs).  The ops of the
+        # rest of the program do not fit the 16-bit immediate: they are a word of the tape's
+        # constants (its derived constants, like the divisor reciprocals) and imm is its offset,
+        # so the word costs no window space and passing through it is two scalar instructions.
+        # A valid lane still passes: dispatch on.  None does: the verdict is false for the whole
+        # wave; the ops go to s36 (one scalar load, this path only) and the tape ends at
+        # tape_bail.  tape_end drains LDS / scalar loads; the only vector load that can be in
+        # flight is the NWIN prefetch, which the next tape start's load_window waits for or
+        # re-issues behind: s[14:15] still names the current block, vector loads land in issue
+        # order, and the bailing tape has issued no store (s59 = 0).
+        # Last handler, so every other handler keeps its offset; the frame is out of s_branch's
+        # reach from here: a pc-relative s_setpc, as the kernel exit's.
+        H(("BAIL",), [f"s_and_b64 s[34:35], {B(0)}, s[62:63]",
+                      f"s_cbranch_scc0 {pfx}_bail_out"]
+          + NEXT_G
+          + [f"{pfx}_bail_out:",
+             "s_lshl_b32 s34, s17, 2",
+             "s_load_dword s36, s[20:21], s34",
+             "s_getpc_b64 s[38:39]",
+             f"{pfx}_bail_pc:",
+             f"s_add_u32 s38, s38, {pfx}_tape_bail - {pfx}_bail_pc",
+             "s_addc_u32 s39, s39, 0xffffffff",
+             "s_waitcnt lgkmcnt(0)",
+             "s_setpc_b64 s[38:39]"], tail=False, reads_stack=False)
     subs = sub_abs_cneg(pfx) + sub_udiv32(pfx) + (sub_uf1(pfx) + sub_udivv(pfx) if G else [])
     return hs, subs
 
@@ -1989,13 +2016,16 @@ def frame(variant, pfx, handlers, subs):
         "s_mov_b32 s78, s84",
         "s_mov_b32 s79, s87",
         "s_mov_b32 s100, s82",
-    ] + NEXT_P) + ([] if G else [
+    ] + NEXT_P) + [
         # a BAIL handler left the tape early: s36 = the ops it skipped (the tape end adds the
-        # whole tape's: the ops counter is of executed ops; pairs and nodes count decided pairs)
+        # whole tape's: the ops counter is of executed ops; pairs and nodes count decided pairs).
+        # B(0) & valid is zero, so first-hit mode records nothing and verdict mode stores zeros.
+        # (G: the tape issued no vector store so far and s[14:15] is the block it left in, which
+        # is all load_window(first) needs for the next descriptor)
         f"{pfx}_tape_bail:",
         "s_sub_u32 s44, s44, s36",
         "s_subb_u32 s45, s45, 0",
-    ]) + [
+    ] + [
         f"{pfx}_tape_end:",
         "s_waitcnt lgkmcnt(0)",
     ] + (prof_point("F_ENDW") if G else []) + [

@@ -315,8 +315,9 @@ static constexpr int64_t kDenseMaxE = 16;
 
 // the assembly interpreter keeps temps in LDS (2 KB per temp per wave, 4 waves per workgroup)
 static constexpr int kQsaMaxTemps = 16;
-// bail points (gprog.h G_BAIL) go on the tapes whose variables P preloads: only P takes them
-static_assert(CompileLimits{}.bail_var_limit == kQsaVars, "bail points are for the tapes P can run");
+// by default bail points (gprog.h G_BAIL) go on the tapes whose variables P preloads: only P takes
+// them unless MQ_G_BAIL=1 lifts the limit (tape_compiler.h g_bail_enabled)
+static_assert(CompileLimits{}.bail_var_limit == kQsaVars, "by default bail points are for the tapes P can run");
 
 // HIP C++ interpreter variants (qs_kernels.hip launch_qs): limbs per stack slot and whether the
 // variant carries the interpreted-keccak handler.  Kind 0 (L = 8) is where 256-bit tapes the
@@ -479,6 +480,7 @@ struct mq_tapes {
   std::vector<GDesc> qbase;                  // their descriptors (const_base into consts)
   uint64_t qsa_gen = ~0ull;                  // layout_gen of the current translation
   bool qsa_live = false;                     // the translation succeeded for every tape
+  bool g_bail = false;                       // uploaded under MQ_G_BAIL=1: G keeps the bail points
   int q_count[2] = {0, 0}, q_temps[2] = {0, 0};
   // G kernel preload for the current translation: gpre[var] = VGPR slot (or -1) of the (at
   // most 8) variables the G tapes push most; g_var_row = their limb rows (QArgs.var_row)
@@ -1794,10 +1796,13 @@ static inline int qsa_depth(const CompiledTape& x, int k) { return (k == 1 && !x
 // not known yet, any variable / lookup is assumed expressible).  extra: the tape's derived
 // constants (divisor reciprocals), appended after its own constants in the same order every
 // time.  Returns false if any instruction is outside the interpreter's set (those tapes run on
-// the HIP C++ kernel).
+// the HIP C++ kernel).  g_bail (the batch was uploaded under MQ_G_BAIL=1; verdict tapes only --
+// never column programs, mode 3): for G a bail point becomes its BAIL word where no PUSH_MEM load
+// can be outstanding, and the ops behind every bail point of the program follow the other
+// derived constants in `extra`.
 static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTape& x, std::vector<uint32_t>* out_p,
                           std::vector<uint32_t>* extra_p, const std::vector<int>* gpre = nullptr,
-                          const std::vector<int>* gstage = nullptr) {
+                          const std::vector<int>* gstage = nullptr, bool g_bail = false) {
   std::vector<uint32_t> dummy_out, dummy_extra;
   std::vector<uint32_t>& out = out_p ? *out_p : dummy_out;
   std::vector<uint32_t>& extra = extra_p ? *extra_p : dummy_extra;
@@ -2004,6 +2009,20 @@ static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTap
     drop_last(2);
     emit_k(fk, x, nsel, imm0, data);
   };
+  // G: may a PUSH_MEM's vector loads be outstanding after the words emitted so far?  The final
+  // pass's rule, read backwards: a PUSH_MEM not yet followed by a stack reader (either wait form
+  // of one drains, or finds nothing to drain) or by a handler that waits for vector memory itself
+  auto push_mem_pending = [&]() -> bool {
+    for (size_t i = log.size(); i-- > 0;) {
+      if (log[i].kind == QK_PUSH_MEM) return true;
+      if (kQsaKindLForm[log[i].kind] >= 0 || c->qsa_vm_drain[log[i].kind]) return false;
+    }
+    return false;
+  };
+  // G under g_bail: the ops behind every bail point of the program, kept or dropped, in program
+  // order -- appended to `extra` after the division constants, whose offsets they leave alone (P
+  // translates the unspilled program, with its own bail points, against the same pool)
+  std::vector<uint32_t> bail_ops;
   uint32_t prev_op = G_END, prev_d = 0, prev_imm = 0;
   size_t prev_out = 0;
   int prev_pre = -1;   // preload slot of the variable the previous instruction pushed
@@ -2082,10 +2101,17 @@ static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTap
       if (++pc >= xprog.size()) return false;
       imm2 = xprog[pc];
     }
-    // a bail point is P's only (G drops the word: its pushes in flight and its program window
-    // make leaving mid-program a stage of its own); dropped, it leaves the fusions' view of
-    // the previous instruction untouched
-    if (op == G_BAIL && !P) continue;
+    // a bail point is P's and, under MQ_G_BAIL=1 (g_bail), G's on verdict tapes.  G takes it
+    // only where no PUSH_MEM load can be outstanding (a load landing in a stack register after
+    // the next tape has started would corrupt that tape): at a spine point every push has been
+    // consumed by the compare that made B(0), which the emitted words must confirm.  Dropped, the
+    // word leaves the fusions' view of the previous instruction untouched.  (The ops behind it
+    // are recorded either way: every translation of a program lays its constants out the same.)
+    if (op == G_BAIL && !P) {
+      if (!g_bail) continue;
+      bail_ops.push_back(imm2);
+      if (d != 0 || bail_ops.size() > 0xFFFFu || push_mem_pending()) continue;
+    }
     const size_t out_before = out.size();
     const bool after_const = prev_op == G_PUSH_CONST && (int)prev_d == d;
     int pushed_pre = -1;
@@ -2094,7 +2120,10 @@ static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTap
       case G_END: ok = word(QK_END, 0, -1, 0); break;
       // P: an entry without a constant (an ordinary non-PF_ entry to the constant prefetch
       // pass); its 32-bit immediate is the ops the rest of the program would cost
-      case G_BAIL: ok = d == 0 && word(QK_BAIL, 0, -1, imm2, true); break;
+      // G: the ops do not fit the 16-bit immediate: it is the index into bail_ops here and
+      // becomes the word's offset in the tape's constants below (the handler loads it when it
+      // leaves the tape, and only then)
+      case G_BAIL: ok = d == 0 && (P ? word(QK_BAIL, 0, -1, imm2, true) : word(QK_BAIL, 0, -1, (uint32_t)bail_ops.size() - 1)); break;
       case G_PUSH_VAR:
       case G_PUSH_VAR_B: {
         const bool b = op == G_PUSH_VAR_B;
@@ -2380,9 +2409,16 @@ static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTap
     // prefetch of the next program window (gen_qsa.py load_window) stays in flight
     // (MQ_NO_LWAIT: no _L variants; END_V is needed either way)
     bool pending = false;
+    std::vector<const Emit*> unsafe_bails;
     for (const Emit& e : log) {
       if (e.kind == QK_PUSH_MEM) {
         pending = true;
+        continue;
+      }
+      if (e.kind == QK_BAIL) {
+        // this pass is the authority on loads in flight: a bail word it finds behind an
+        // outstanding PUSH_MEM goes (push_mem_pending kept it out when it was emitted)
+        if (pending) unsafe_bails.push_back(&e);
         continue;
       }
       if (e.kind == QK_END) {
@@ -2401,6 +2437,20 @@ static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTap
       }
       if (c->qsa_vm_drain[e.kind]) pending = false;
     }
+    // the kept bail words name their ops by offset in the tape's constants; one past the
+    // immediate's reach goes too
+    const size_t bail_base = x.consts.size() + extra.size();
+    for (const Emit& e : log) {
+      if (e.kind != QK_BAIL) continue;
+      const size_t off = bail_base + e.imm;
+      const bool gone = std::find(unsafe_bails.begin(), unsafe_bails.end(), &e) != unsafe_bails.end();
+      if (off > 0xFFFFu && !gone) unsafe_bails.push_back(&e);
+      else if (!gone) out[e.pos] = (out[e.pos] & 0xFFFFu) | ((uint32_t)off << 16);
+    }
+    extra.insert(extra.end(), bail_ops.begin(), bail_ops.end());
+    std::sort(unsafe_bails.begin(), unsafe_bails.end());   // (log order = position order)
+    for (size_t i = unsafe_bails.size(); i-- > 0;)   // (last first: earlier positions stay valid)
+      out.erase(out.begin() + (long)unsafe_bails[i]->pos, out.begin() + (long)ends_at(*unsafe_bails[i]));
   }
   if (P) {
     // constant prefetch (gen_qsa.py NEXT_P): a constant handler whose predecessor is not itself
@@ -2458,6 +2508,9 @@ static int tapes_upload_one(mq_ctx* c, int32_t n_tapes, std::vector<CompiledTape
     c->live_tapes.insert(T.get());
   }
   T->n_tapes = n_tapes;
+  // (the flag the compile just read: every translation of this batch, now and per model layout
+  // later, must lay the tapes' derived constants out the same)
+  T->g_bail = g_bail_enabled();
   T->unsupported.assign(std::max(n_tapes, 1), 0);
   T->n_nodes.assign(n_tapes, 0);
   T->alg_ops.assign(n_tapes, 0);
@@ -2488,7 +2541,7 @@ static int tapes_upload_one(mq_ctx* c, int32_t n_tapes, std::vector<CompiledTape
     parallel_for(n_tapes, 32, [&](int, int64_t b, int64_t e) {
       for (int64_t t = b; t < e; t++)
         if (ct[t].supported && ct[t].L == 8 && ct[t].n_temps <= kQsaMaxTemps)
-          qsa_ok[t] = qsa_translate(c, 1, false, ct[t], nullptr, &qextra[t]) ? 1 : 0;
+          qsa_ok[t] = qsa_translate(c, 1, false, ct[t], nullptr, &qextra[t], nullptr, nullptr, T->g_bail) ? 1 : 0;
     });
   pt.reset(new PhaseTimer(&c->host_t[2]));
   // (before the descriptor passes: with may_move they empty the eligible tapes' vectors)
@@ -4110,6 +4163,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   std::vector<std::vector<uint32_t>> trs(nq);
   std::vector<char> kind_of(nq, 0);
   std::atomic<bool> g_fail{false};
+  const bool g_bail = T->g_bail;   // (uploaded under MQ_G_BAIL=1: G's verdict tapes keep their bail points)
   parallel_for(nq, 32, [&](int, int64_t b, int64_t e) {
     std::vector<uint32_t> ex;
     for (int64_t i = b; i < e && !g_fail.load(std::memory_order_relaxed); i++) {
@@ -4119,7 +4173,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
       }
       if (on_p[i] && qsa_translate(c, 0, true, T->qct[i], &trs[i], &ex)) continue;
       kind_of[i] = 1;
-      if (!qsa_translate(c, 1, true, T->qct[i], &trs[i], &ex, &T->gpre, &T->gstage)) {
+      if (!qsa_translate(c, 1, true, T->qct[i], &trs[i], &ex, &T->gpre, &T->gstage, g_bail)) {
         g_fail = true;
         break;
       }

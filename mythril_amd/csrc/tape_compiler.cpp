@@ -123,6 +123,11 @@ struct Fail {
 
 static double node_alg_ops(const mq_node* nd, int64_t i);
 
+bool g_bail_enabled() {
+  const char* e = std::getenv("MQ_G_BAIL");
+  return e && *e && *e != '0';
+}
+
 CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLimits& lim) {
   CompiledTape out;
   const int64_t base = batch->tape_offsets[t];
@@ -135,6 +140,9 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
   const mq_node* nd = batch->nodes + base;
   // conjunction spine with bail points (verdict tapes only; read per compile: tests flip it)
   bool bail_on = !lim.value_root && std::getenv("MQ_NO_BAIL") == nullptr;
+  // MQ_G_BAIL=1 (opt-in): the G interpreter takes bail points too, so tapes reading any variable
+  // get the spine (MQ_NO_BAIL=1 still removes every bail point)
+  const int bail_var_limit = g_bail_enabled() ? kMaxImm + 1 : lim.bail_var_limit;
   double bail_min_ops = kBailMinOps;
   if (const char* e = std::getenv("MQ_BAIL_MIN_OPS")) bail_min_ops = std::max(1.0, std::atof(e));
   try {
@@ -298,9 +306,9 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
         case MQ_OP_CONST: r = konst(i); break;
         case MQ_OP_VAR: {
           if (n.a > (uint32_t)kMaxImm) throw Fail{"var index too large"};
-          // only the P interpreter takes bail points, and it runs tapes over its preloaded
-          // variables only: any other tape keeps today's program
-          if (n.a >= (uint32_t)lim.bail_var_limit) bail_on = false;
+          // by default only the P interpreter takes bail points, and it runs tapes over its
+          // preloaded variables only: any other tape keeps today's program
+          if (n.a >= (uint32_t)bail_var_limit) bail_on = false;
           INode x = mk(w == 0 ? G_PUSH_VAR_B : G_PUSH_VAR, w, {}, n.a);
           x.leaf = true;
           r = B.add(x);

@@ -66,13 +66,19 @@ struct CompileLimits {
   int g_depth = 0;            // > 0: also build prog_g for a stack of this many slots
   bool value_root = false;    // column program: any BV/Bool root, its value is the result
   // conjunction spine and bail points (gprog.h G_BAIL) only for tapes whose variables all have
-  // an index below this: the P interpreter's preloaded variables (gen_qsa.py NV).  The G
-  // interpreter drops the word, and the spine's conjunct order alone measured a hair slower
+  // an index below this: the P interpreter's preloaded variables (gen_qsa.py NV).  By default the
+  // G interpreter drops the word, and the spine's conjunct order alone measured a hair slower
   // there (C3 16.25 against 16.16 ms), so its tapes keep their programs.  (The index is all
   // the compiler knows: a tape over variables 0-7 that P cannot run -- an op it lacks, more than
   // its six slots -- still gets the spine, and G runs it with the words dropped.)
+  // MQ_G_BAIL=1 lifts the limit for verdict compiles: G then takes the bail points
+  // (g_bail_enabled; gen_qsa.py G BAIL handler).
   int bail_var_limit = 8;
 };
+
+// MQ_G_BAIL=1 (opt-in, read per call: tests flip it): bail points on the G interpreter -- the
+// compiler puts the spine on tapes reading any variable, the G translator keeps the G_BAIL words.
+bool g_bail_enabled();
 
 // Compile tape t of the batch. n_funcs/funcs describe the model function table (result
 // widths); pass n_funcs = -1 when unknown (UF widths are then taken from the nodes).
