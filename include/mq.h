@@ -592,6 +592,28 @@ int mq_tape_program(const mq_tape_batch* batch, int32_t t, uint32_t* words, int3
 int mq_tape_program_g(const mq_tape_batch* batch, int32_t t, uint32_t* words, int32_t cap, int32_t* n_words,
                       int32_t* depth_g, int32_t* n_temps_g, int32_t* spilled);
 
+/* Host-only: the low-limb prefilter program of tape t (gprog.h PfOp: two words an instruction,
+   PF_END last) into words[cap]; *n_words = its length, 0 when the tape has none (no eligible EQ
+   conjunct, MQ_PREFILTER=0 or MQ_NO_BAIL=1); *pf_alg_ops its SURVEY §8(d) cost at one limb,
+   *depth its stack slots (each may be NULL).  Returns 0, MQ_ERR_ARG or MQ_ERR_TAPE. */
+int mq_tape_prefilter_program(const mq_tape_batch* batch, int32_t t, uint32_t* words, int32_t cap, int32_t* n_words,
+                              double* pf_alg_ops, int32_t* depth);
+
+/* Of the current translation: *n_prefiltered = tapes on the P interpreter with a prefilter
+   program; *ran = whether the last first-hit launch ran the prefilter launch in front of P (it
+   does from 4096 models of a device's shard on; MQ_PREFILTER=force always, =0 never; never for
+   verdicts or a latency-bound launch).  Each may be NULL. */
+int mq_tapes_prefilter_split(mq_tapes* tapes, int32_t* n_prefiltered, int32_t* ran);
+
+/* Diagnostic: the (block, descriptor) bitmap the last launch's prefilter left on the lead device,
+   *rows = ceil(M / 64) rows of *words_per_row words into words[cap_words] (nothing copied when
+   too small); bit (d & 31) of word d >> 5 of row b set = P descriptor d stayed alive for models
+   [64 b, 64 b + 64).  desc_tape[d] / desc_has[d] (cap_desc entries each, *n_desc used) = the
+   descriptor's tape and whether it has a prefilter program (bits of the others are never set:
+   P runs them everywhere).  *rows = 0 when the last launch did not run the prefilter. */
+int mq_tapes_prefilter_alive(mq_tapes* tapes, uint32_t* words, int64_t cap_words, int64_t* rows, int32_t* words_per_row,
+                             int32_t* desc_tape, uint8_t* desc_has, int32_t cap_desc, int32_t* n_desc);
+
 /* Library version string. */
 const char* mq_version(void);
 

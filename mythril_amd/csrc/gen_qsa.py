@@ -13,6 +13,11 @@ Two variants are generated from the same handler code (one asm statement each, l
 
   P ("preload", qsa_kernel):  the wave's 64 models' first 8 variables are preloaded into VGPRs
      once per workgroup; PUSH_VAR is a register copy.  C2-shaped batches.
+     Frame mode 4 (pf_frame, behind the handlers) is the low-limb prefilter: the same register
+     map holds limb 0 of eight 64-model blocks, narrow handlers (ADD32 .. EQK32, the last ones)
+     run a tape's cheapest EQ conjunct at 32 bits and a (block, tape) bitmap keeps what survives;
+     in first-hit mode with that bitmap (QArgs.alive) a wave runs only its block's live tapes
+     (alive_scan).
   G ("general", qsg_kernel):  variables pushed from the model rows in HBM (PUSH_MEM: the loads
      are issued by the push and waited for by the first consumer) or from rows staged in LDS;
      table-lookup subroutine (UF1).  EVM-shaped batches and hoisted column programs (mode 3).
@@ -1656,8 +1661,239 @@ def make_handlers(variant, pfx):
              "s_addc_u32 s39, s39, 0xffffffff",
              "s_waitcnt lgkmcnt(0)",
              "s_setpc_b64 s[38:39]"], tail=False, reads_stack=False)
+    if not G:
+        # ---- P, prefilter mode (frame mode 4, pf_frame): narrow handlers on the low limb of
+        # eight 64-model blocks, S[d][l] = slot d of block l.  PUSH_VAR, BAND, BOR, BXOR and BNOT
+        # above serve the mode unchanged.  The constant forms take the constant's low limb from
+        # the entry's 32-bit immediate (s17).  EQ32 / EQK32 end the program: eight lane masks
+        # (PF_R), each AND-ed with its block's valid lanes (PF_VM), then the mode's tape end.
+        # Last handlers: every other handler keeps its offset, and the mode's frame follows them
+        # within s_branch's reach.
+        for d in range(1, D):
+            a = d - 1
+            H(("ADD32", d), [f"v_add_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)])
+            H(("SUB32", d), [f"v_sub_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)])
+            H(("MUL32", d), [f"v_mul_lo_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)])
+        for d in range(D):
+            H(("NEG32", d), [f"v_sub_u32 {S(d, l)}, 0, {S(d, l)}" for l in range(L)])
+            H(("PUSH_K32", d), [f"v_mov_b32 {S(d, l)}, s17" for l in range(L)], reads_stack=False)
+            H(("ADDK32", d), [f"v_add_u32 {S(d, l)}, s17, {S(d, l)}" for l in range(L)])
+            H(("MULK32", d), [f"v_mul_lo_u32 {S(d, l)}, {S(d, l)}, s17" for l in range(L)])
+            for nm, ins in (("ANDK32", "v_and_b32"), ("ORK32", "v_or_b32"), ("XORK32", "v_xor_b32")):
+                H((nm, d), [f"{ins} {S(d, l)}, s17, {S(d, l)}" for l in range(L)])
+        # (a VALU write of an SGPR is read by the SALU after >= 4 wait states: s_nop 3)
+        pf_and = ["s_nop 3"] + [f"s_and_b64 {PF_R[l]}, {PF_R[l]}, {PF_VM[l]}" for l in range(L)] + [f"s_branch {pfx}_pf_tape_end"]
+        for d in range(1, D):
+            H(("EQ32", d), [f"v_cmp_eq_u32_e64 {PF_R[l]}, {S(d - 1, l)}, {S(d, l)}" for l in range(L)] + pf_and, tail=False)
+        for d in range(D):
+            H(("EQK32", d), [f"v_cmp_eq_u32_e64 {PF_R[l]}, s17, {S(d, l)}" for l in range(L)] + pf_and, tail=False)
     subs = sub_abs_cneg(pfx) + sub_udiv32(pfx) + (sub_uf1(pfx) + sub_udivv(pfx) if G else [])
     return hs, subs
+
+
+# P prefilter mode: the eight blocks' result masks (eq_body's scratch pairs) and valid-lane masks
+# (the Bool stack, the tile's valid mask and &best[tape]: all unused in the mode)
+PF_R = ["s[34:35]", "s[36:37]", "s[38:39]", "s[60:61]", "s[64:65]", "s[66:67]", "s[68:69]", "s[70:71]"]
+PF_VM = [f"s[{BBASE + 2 * l}:{BBASE + 2 * l + 1}]" for l in range(6)] + ["s[62:63]", "s[72:73]"]
+S_NOP0 = "s_nop 0"
+
+
+def long_jump(target, tag, back=False, pad=0, link=False):
+    """pc-relative jump beyond s_branch's reach through s[34:35] (back: the target precedes the
+    jump; link: s_swappc, the return address in s[76:77]); pad: s_nop words after it (never
+    executed on the way through: they keep the alignment of what follows)."""
+    out = ["s_getpc_b64 s[34:35]", f"{tag}:",
+           f"s_add_u32 s34, s34, {target} - {tag}",
+           f"s_addc_u32 s35, s35, {'0xffffffff' if back else '0'}",
+           "s_swappc_b64 s[76:77], s[34:35]" if link else "s_setpc_b64 s[34:35]"]
+    return out + [S_NOP0] * pad
+
+
+def alive_scan(pfx, first):
+    """P first-hit mode with a prefilter bitmap (QArgs.alive): the next descriptor at or after s24
+    (below the group's end s94) whose bit is set in alive[block s95] | alive_static.  Found: s24 =
+    it, s25 = s24 + 1 (the tape loop runs that tape alone and comes back through tapes_done).
+    first (before the variable preload): found returns to the prologue (s[76:77]), none leaves
+    the kernel, no counters to flush.  Otherwise found enters the tape body, none returns to the
+    counter flush."""
+    k = "a" if first else "b"
+    found = ["s_setpc_b64 s[76:77]"] if first else long_jump(f"{pfx}_tape_body", f"{pfx}_asj{k}", back=True)
+    none = [f"s_branch {pfx}_end"] if first else ["s_setpc_b64 s[76:77]"]
+    return [
+        f"{pfx}_alive_scan_{k}:",
+        "s_cmp_ge_u32 s24, s94",
+        f"s_cbranch_scc1 {pfx}_as_none{k}",
+        "s_load_dwordx4 s[64:67], s[10:11], 0x1b8",     # alive, alive_static
+        "s_load_dword s68, s[10:11], 0x1d0",            # words per row
+        "s_waitcnt lgkmcnt(0)",
+        "s_mul_hi_u32 s37, s95, s68",
+        "s_mul_i32 s36, s95, s68",
+        "s_lshl_b64 s[36:37], s[36:37], 2",
+        "s_add_u32 s64, s64, s36",
+        "s_addc_u32 s65, s65, s37",
+        f"{pfx}_as_loop{k}:",
+        "s_lshr_b32 s34, s24, 5",
+        "s_lshl_b32 s35, s34, 2",
+        "s_load_dword s36, s[64:65], s35",
+        "s_load_dword s37, s[66:67], s35",
+        "s_waitcnt lgkmcnt(0)",
+        "s_or_b32 s36, s36, s37",
+        "s_lshr_b32 s36, s36, s24",                     # (shift by s24 & 31) bits from s24 on
+        "s_cmp_eq_u32 s36, 0",
+        f"s_cbranch_scc0 {pfx}_as_bit{k}",
+        "s_add_u32 s34, s34, 1",
+        "s_lshl_b32 s24, s34, 5",
+        "s_cmp_lt_u32 s24, s94",
+        f"s_cbranch_scc1 {pfx}_as_loop{k}",
+        f"s_branch {pfx}_as_none{k}",
+        f"{pfx}_as_bit{k}:",
+        "s_ff1_i32_b32 s36, s36",
+        "s_add_u32 s24, s24, s36",
+        "s_cmp_ge_u32 s24, s94",
+        f"s_cbranch_scc1 {pfx}_as_none{k}",
+        "s_add_u32 s25, s24, 1",
+    ] + found + [f"{pfx}_as_none{k}:"] + none
+
+
+def pf_frame(pfx):
+    """P frame mode 4, the low-limb prefilter: a workgroup's tile is 2 048 models, a wave's 512 =
+    eight 64-model blocks; V[v][l] = limb 0 of variable v at model base + 64 l + lane (clamped
+    to M - 1), so every dispatch serves 512 models.  The tape loop walks pf_descs (parallel to the
+    P launch's descs; prog_len 0: no prefilter).  A tape no valid lane passes is decided for the
+    wave's blocks; for a block with a surviving lane bit (desc & 31) of alive[block][desc >> 5] is
+    set, one lane's vector atomic.  Counters: pairs and node-evals of the blocks cleared (all the
+    wave's valid lanes minus the survivors' blocks), ops of the narrow programs run."""
+    OFF = [T(l) for l in range(L)]    # byte offset of the lane's model in block l
+    P = [f"{pfx}_pf_main:",
+         "v_and_b32 v4, 63, v3",
+         "v_lshrrev_b32 v5, 6, v3",
+         "s_nop 1",
+         "v_readfirstlane_b32 s34, v5",
+         "s_load_dwordx2 s[26:27], s[10:11], 0x1b8",    # alive
+         "s_load_dwordx2 s[22:23], s[10:11], 0x1c8",    # pf_descs
+         "s_load_dword s101, s[10:11], 0x1d0",          # bitmap words per row
+         "s_nop 3",
+         "s_lshl_b32 s28, s96, 11",
+         "s_lshl_b32 s36, s34, 9",
+         "s_add_u32 s28, s28, s36",                     # the wave's first model
+         "s_cmp_ge_u32 s28, s29",
+         f"s_cbranch_scc1 {pfx}_end",
+         "s_lshr_b32 s95, s28, 6",                      # its first block
+         "s_sub_u32 s37, s29, 1",
+         "v_add_u32 v2, s28, v4"]
+    for l in range(L):
+        P += [f"v_add_u32 v5, {64 * l}, v2",
+              f"v_cmp_lt_u32_e64 {PF_VM[l]}, v5, s29",
+              "v_min_u32 v5, s37, v5",
+              f"v_lshlrev_b32 {OFF[l]}, 2, v5"]
+    P += ["s_mov_b64 s[40:41], 0", "s_mov_b64 s[42:43], 0", "s_mov_b64 s[44:45], 0",
+          "s_mov_b32 s100, 0",                          # survivors: pairs (s[74:75], below: node-evals)
+          "s_mul_i32 s24, s97, s83", "s_add_u32 s25, s24, s83", "s_min_u32 s25, s25, s82",
+          "s_mov_b64 s[20:21], s[46:47]",               # the dispatch tail's constant prefetch: any mapped address
+          "s_waitcnt lgkmcnt(0)"]
+    # limb 0 of the 8 variables (row index table at args+0x60, entries 8 v)
+    for c in range(NV * L // 16):
+        P += [f"s_load_dwordx16 s[64:79], s[10:11], {0x60 + 64 * c:#x}", "s_waitcnt lgkmcnt(0)"]
+        for j in (0, 8):
+            v = 2 * c + j // 8
+            P += [f"s_mul_i32 s34, s{64 + j}, s29", f"s_mul_hi_u32 s35, s{64 + j}, s29",
+                  "s_lshl_b64 s[34:35], s[34:35], 2", "s_add_u32 s34, s34, s90", "s_addc_u32 s35, s35, s91"]
+            P += [f"global_load_dword v{VBASE + 8 * v + l}, {OFF[l]}, s[34:35]" for l in range(L)]
+    # (s[72:73] = PF_VM[7] was among the row indices: its mask again)
+    P += [f"v_add_u32 v5, {64 * 7}, v2", f"v_cmp_lt_u32_e64 {PF_VM[7]}, v5, s29",
+          "s_mov_b64 s[74:75], 0",
+          "s_waitcnt vmcnt(0)",
+          "s_cmp_ge_u32 s24, s25",
+          f"s_cbranch_scc1 {pfx}_pf_done",
+          f"{pfx}_pf_tape_body:",
+          "s_lshl_b32 s34, s24, 5",
+          "s_load_dwordx8 s[80:87], s[22:23], s34",
+          "s_waitcnt lgkmcnt(0)",
+          "s_cmp_eq_u32 s81, 0",
+          f"s_cbranch_scc1 {pfx}_pf_next",
+          "s_lshl_b32 s34, s80, 2",
+          "s_add_u32 s14, s46, s34",
+          "s_addc_u32 s15, s47, 0",
+          "s_load_dwordx4 s[96:99], s[14:15], 0x0",
+          "s_mov_b32 s16, 12",
+          "s_mov_b32 s78, s84",
+          "s_mov_b32 s79, s87"] + NEXT_P
+    P += [f"{pfx}_pf_tape_end:",
+          "s_waitcnt lgkmcnt(0)",                        # the entry and constant prefetches in flight
+          "s_add_u32 s40, s40, 1",
+          "s_add_u32 s42, s42, s78", "s_addc_u32 s43, s43, 0",
+          "s_add_u32 s44, s44, s79", "s_addc_u32 s45, s45, 0",
+          f"s_or_b64 s[76:77], {PF_R[0]}, {PF_R[1]}"]
+    P += [f"s_or_b64 s[76:77], s[76:77], {PF_R[l]}" for l in range(2, L)]
+    P += [f"s_cbranch_scc1 {pfx}_pf_rare",
+          f"{pfx}_pf_next:",
+          "s_add_u32 s24, s24, 1",
+          "s_cmp_lt_u32 s24, s25",
+          f"s_cbranch_scc1 {pfx}_pf_tape_body",
+          f"{pfx}_pf_done:",
+          f"s_bcnt1_i32_b64 s38, {PF_VM[0]}"]
+    for l in range(1, L):
+        P += [f"s_bcnt1_i32_b64 s34, {PF_VM[l]}", "s_add_u32 s38, s38, s34"]
+    P += ["s_mul_hi_u32 s41, s40, s38",
+          "s_mul_i32 s40, s40, s38",
+          "s_sub_u32 s40, s40, s100",
+          "s_subb_u32 s41, s41, 0",
+          "s_mul_i32 s43, s43, s38",
+          "s_mul_hi_u32 s34, s42, s38",
+          "s_add_u32 s43, s43, s34",
+          "s_mul_i32 s42, s42, s38",
+          "s_sub_u32 s42, s42, s74",
+          "s_subb_u32 s43, s43, s75",
+          "s_mul_i32 s45, s45, s38",
+          "s_mul_hi_u32 s34, s44, s38",
+          "s_add_u32 s45, s45, s34",
+          "s_mul_i32 s44, s44, s38",
+          "s_xor_b32 s34, s95, s25",
+          "s_and_b32 s34, s34, 255",
+          "s_lshl_b32 s34, s34, 7",
+          "s_mov_b64 s[60:61], exec",
+          "s_mov_b64 exec, 1",
+          "v_mov_b32 v6, s34",
+          "v_mov_b32 v4, s40",
+          "v_mov_b32 v5, s41",
+          "global_atomic_add_x2 v6, v[4:5], s[92:93]",
+          "v_mov_b32 v4, s42",
+          "v_mov_b32 v5, s43",
+          "global_atomic_add_x2 v6, v[4:5], s[92:93] offset:8",
+          "v_mov_b32 v4, s44",
+          "v_mov_b32 v5, s45",
+          "global_atomic_add_x2 v6, v[4:5], s[92:93] offset:16",
+          "s_waitcnt vmcnt(0)",
+          "s_mov_b64 exec, s[60:61]",
+          f"s_branch {pfx}_end",
+          f"{pfx}_pf_rare:"]
+    for l in range(L):
+        P += [f"s_cmp_eq_u64 {PF_R[l]}, 0",
+              f"s_cbranch_scc1 {pfx}_pf_r{l}",
+              f"s_bcnt1_i32_b64 s80, {PF_VM[l]}",
+              "s_add_u32 s100, s100, s80",
+              "s_mul_i32 s80, s80, s78",
+              "s_add_u32 s74, s74, s80",
+              "s_addc_u32 s75, s75, 0",
+              f"s_add_u32 s80, s95, {l}",
+              "s_mul_hi_u32 s81, s80, s101",
+              "s_mul_i32 s80, s80, s101",
+              "s_lshr_b32 s83, s24, 5",
+              "s_add_u32 s80, s80, s83",
+              "s_addc_u32 s81, s81, 0",
+              "s_lshl_b64 s[80:81], s[80:81], 2",
+              "s_add_u32 s80, s80, s26",
+              "s_addc_u32 s81, s81, s27",
+              "s_lshl_b32 s82, 1, s24",
+              "s_mov_b64 s[84:85], exec",
+              "s_mov_b64 exec, 1",
+              "v_mov_b32 v5, s82",
+              "v_mov_b32 v6, 0",
+              "global_atomic_or v6, v5, s[80:81]",
+              "s_mov_b64 exec, s[84:85]",
+              f"{pfx}_pf_r{l}:"]
+    P += [f"s_branch {pfx}_pf_next"]
+    return P
 
 
 # ---------------------------------------------------------------- kernel frame
@@ -1795,6 +2031,7 @@ def frame(variant, pfx, handlers, subs):
         "v_mov_b32 v3, %3",
         "s_load_dwordx16 s[64:79], s[10:11], 0x0",
         "s_load_dwordx8 s[80:87], s[10:11], 0x40",
+    ] + ([] if G else ["s_load_dwordx2 s[100:101], s[10:11], 0x1b8"]) + [   # P: the prefilter bitmap (alive)
         "s_waitcnt lgkmcnt(0)",
         "s_mov_b64 s[22:23], s[64:65]",
         "s_mov_b64 s[46:47], s[66:67]",
@@ -1842,7 +2079,16 @@ def frame(variant, pfx, handlers, subs):
         "s_mov_b64 exec, s[36:37]",
         f"s_branch {pfx}_exit",
         f"{pfx}_main:",
-    ] + ([
+    ] + ([] if G else [
+        # P mode 4: the low-limb prefilter (pf_frame, behind the handlers).  (The three P-only
+        # insertions in this frame -- this one, the bitmap scan before the preload and the one at
+        # tapes_done -- are padded to 64 bytes each, so the handlers and the tape loop keep their
+        # offsets within a cache line.)
+        "s_cmp_eq_u32 s31, 4",
+        f"s_cbranch_scc0 {pfx}_main_p",
+    ] + long_jump(f"{pfx}_pf_main", f"{pfx}_pfj", pad=9) + [
+        f"{pfx}_main_p:",
+    ]) + ([
         "v_mbcnt_lo_u32_b32 v39, -1, 0", "v_mbcnt_hi_u32_b32 v39, -1, v39", "v_lshlrev_b32 v39, 2, v39",
     ] if G and LANE4 else []) + [
         # wave / lane / model index
@@ -1882,7 +2128,18 @@ def frame(variant, pfx, handlers, subs):
         "s_mul_i32 s24, s97, s83",
         "s_add_u32 s25, s24, s83",
         "s_min_u32 s25, s25, s82",
-    ] + ([
+    ] + ([] if G else [
+        # P with a prefilter bitmap (QArgs.alive, first-hit mode): s101 != 0; the wave runs only
+        # the tapes live for its block (alive_scan: s94 = the group's end, s95 = the block) and
+        # leaves before the preload when there is none
+        "s_or_b32 s101, s100, s101",
+        "s_cmp_eq_u32 s101, 0",
+        f"s_cbranch_scc1 {pfx}_no_alive",
+        "s_mov_b32 s94, s25",
+        "s_lshr_b32 s95, s35, 6",
+    ] + long_jump(f"{pfx}_alive_scan_a", f"{pfx}_asa", pad=4, link=True) + [
+        f"{pfx}_no_alive:",
+    ]) + ([
         # G mode 3: a column level's groups are uneven (balanced by cost, mq_api.cpp
         # balance_groups): group g spans descriptors [t[g], t[g+1]) of the u32 table t at
         # args+0x38 (table_out, which only mode 2 writes)
@@ -2079,7 +2336,13 @@ def frame(variant, pfx, handlers, subs):
         "s_cmp_lt_u32 s24, s25",
         f"s_cbranch_scc1 {pfx}_tape_body",
         f"{pfx}_tapes_done:",
-    ] + ([
+    ] + ([] if G else [
+        # P with a prefilter bitmap: on to the block's next live tape, if any
+        "s_cmp_eq_u32 s101, 0",
+        f"s_cbranch_scc1 {pfx}_tapes_flush",
+    ] + long_jump(f"{pfx}_alive_scan_b", f"{pfx}_asb", pad=9, link=True) + [
+        f"{pfx}_tapes_flush:",
+    ]) + ([
         "v_mbcnt_lo_u32_b32 v6, -1, 0", "v_mbcnt_hi_u32_b32 v6, -1, v6", "v_lshlrev_b32 v6, 3, v6",
         f"v_add_u32 v7, {PROF_VGPR}, v6",
         "s_load_dwordx2 s[64:65], s[10:11], 0x1a8",
@@ -2133,6 +2396,10 @@ def frame(variant, pfx, handlers, subs):
             P.append(".p2align 3")
         P.append(f"{pfx}_h{k}:  ; {' '.join(map(str, key))}")
         P += body
+    if not G:
+        # behind the handlers (whose offsets stay what they were): the prefilter mode's frame and
+        # the bitmap scans of first-hit mode
+        P += pf_frame(pfx) + alive_scan(pfx, True) + alive_scan(pfx, False)
     P.append(f"{pfx}_end:")
     return P
 

@@ -121,5 +121,40 @@ struct GDesc {
 
 constexpr int kMaxImm = (1 << 20) - 1;
 
+// Low-limb prefilter program (CompiledTape::prog_pf): a self-contained stack program over the
+// low 32 bits of every value, two words an instruction: op[7:0] | d[11:8], then a full 32-bit
+// immediate.  Slots as above (binary ops: operands d-1 and d, result in d-1; the ...K forms and
+// the unary ops work on slot d in place with the immediate as their right operand).  The last
+// instruction is PF_EQ or PF_EQK, then PF_END.  A false result proves the tape false; a true one
+// proves nothing.
+enum PfOp : uint32_t {
+  PF_END = 0,
+  PF_PUSH_VAR = 1,   // imm = var index (limb 0)
+  PF_PUSH_K = 2,     // imm = the constant's low limb
+  PF_ADD = 3,
+  PF_SUB = 4,
+  PF_MUL = 5,
+  PF_NEG = 6,
+  PF_BAND = 7,
+  PF_BOR = 8,
+  PF_BXOR = 9,
+  PF_BNOT = 10,
+  PF_ADDK = 11,
+  PF_MULK = 12,
+  PF_ANDK = 13,
+  PF_ORK = 14,
+  PF_XORK = 15,
+  PF_EQ = 16,
+  PF_EQK = 17,
+  PF_NUM_OPS = 18
+};
+static inline uint32_t pfword(uint32_t op, uint32_t d) { return op | (d << 8); }
+// SURVEY §8(d) cost of a narrow instruction (L = 1: a multiplication L (L + 1), the rest L)
+static inline double pf_op_cost(uint32_t op) {
+  return op == PF_MUL || op == PF_MULK ? 2.0 : (op == PF_END || op == PF_PUSH_VAR || op == PF_PUSH_K) ? 0.0 : 1.0;
+}
+constexpr int kPfMaxDepth = 6;    // stack slots of a prefilter program
+constexpr int kPfMaxInstr = 48;   // its longest form, instructions without PF_END
+
 }  // namespace mq
 #endif

@@ -495,9 +495,18 @@ struct mq_tapes {
   // [1] G tapes, [2] G column programs; qpairs = (kind, next kind) counts over the G tapes,
   // qpairs_p over the P tapes
   std::vector<int64_t> qhist[3], qpairs, qpairs_p;
-  DevBuf qdescs, qprog, qargs[2];
-  QArgs qargs_dev_copy[2];   // what qargs[k] currently holds on the device
-  bool qargs_valid[2] = {false, false};
+  DevBuf qdescs, qprog, qargs[3];   // [2]: the prefilter launch's (P, mode 4)
+  QArgs qargs_dev_copy[3];   // what qargs[k] currently holds on the device
+  bool qargs_valid[3] = {false, false, false};
+  // low-limb prefilter of the current translation: pf_descs parallel to the P descriptors
+  // (prog_len 0: none), pf_static = the bitmap row of the descriptors without one, pf_alive the
+  // (block, descriptor) bitmap a launch fills; pf_count = P tapes with a prefilter program
+  DevBuf pf_descs, pf_static, pf_alive;
+  int pf_count = 0, pf_words = 0;
+  bool pf_ran = false;        // the last launch ran the prefilter
+  int64_t pf_rows = 0;        // bitmap rows of that launch
+  std::vector<int32_t> pf_tape;   // per P descriptor: its tape, and whether it has a prefilter program
+  std::vector<uint8_t> pf_has;
   // batch-level hoisting: column programs evaluated once per model before the tapes, one
   // launch per (nesting level, kernel variant); GDesc.tape = the model variable written
   // v8 begins with the v8q columns the G assembly interpreter can take (structurally); when
@@ -2597,6 +2606,7 @@ static int tapes_upload_one(mq_ctx* c, int32_t n_tapes, std::vector<CompiledTape
   if (descs.empty()) descs.push_back(GDesc{});
   HIPCHK(T->qargs[0].ensure(sizeof(QArgs)));
   HIPCHK(T->qargs[1].ensure(sizeof(QArgs)));
+  HIPCHK(T->qargs[2].ensure(sizeof(QArgs)));
   // P's constant prefetch reads 8 words at a tape's constants + 0 even for a tape without any
   consts.insert(consts.end(), 8, 0u);
   {
@@ -4064,6 +4074,51 @@ static void fca_plan(const mq_ctx* c, const std::vector<std::vector<uint32_t>>& 
   close();
 }
 
+// A tape's low-limb prefilter program (CompiledTape::prog_pf) as P entries for frame mode 4:
+// (handler address, the instruction's 32-bit immediate, 0).  PUSH_VAR and the bitwise ops are
+// P's own handlers (on the narrow register map they act on eight blocks' low limbs).
+static bool qsa_translate_pf(const mq_ctx* c, const CompiledTape& x, std::vector<uint32_t>& out) {
+  out.clear();
+  if (x.depth_pf > kQsaStackP) return false;
+  for (size_t pc = 0; pc + 1 < x.prog_pf.size(); pc += 2) {
+    const uint32_t op = x.prog_pf[pc] & 0xFFu, imm = x.prog_pf[pc + 1];
+    const int d = (int)((x.prog_pf[pc] >> 8) & 0xFu);
+    int kind = -1, v = -1;
+    uint32_t im = imm;
+    switch (op) {
+      case PF_END: kind = QK_END; break;
+      case PF_PUSH_VAR:
+        if (imm >= (uint32_t)kQsaVars) return false;
+        kind = QK_PUSH_VAR, v = (int)imm, im = 0;
+        break;
+      case PF_PUSH_K: kind = QK_PUSH_K32; break;
+      case PF_ADD: kind = QK_ADD32; break;
+      case PF_SUB: kind = QK_SUB32; break;
+      case PF_MUL: kind = QK_MUL32; break;
+      case PF_NEG: kind = QK_NEG32; break;
+      case PF_BAND: kind = QK_BAND; break;
+      case PF_BOR: kind = QK_BOR; break;
+      case PF_BXOR: kind = QK_BXOR; break;
+      case PF_BNOT: kind = QK_BNOT; break;
+      case PF_ADDK: kind = QK_ADDK32; break;
+      case PF_MULK: kind = QK_MULK32; break;
+      case PF_ANDK: kind = QK_ANDK32; break;
+      case PF_ORK: kind = QK_ORK32; break;
+      case PF_XORK: kind = QK_XORK32; break;
+      case PF_EQ: kind = QK_EQ32; break;
+      case PF_EQK: kind = QK_EQK32; break;
+      default: return false;
+    }
+    if (d >= kQsaStackP) return false;
+    const int h = c->qsa_index[0][kind][kind == QK_END ? 0 : d][v + 1];
+    if (h < 0) return false;
+    out.push_back(c->qsa_hbase_lo[0] + c->qsa_off[0][h]);
+    out.push_back(im);
+    out.push_back(0);
+  }
+  return !out.empty();
+}
+
 static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   if (T->qsa_gen == c->layout_gen) return MQ_OK;
   T->qsa_gen = c->layout_gen;
@@ -4181,6 +4236,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
     }
   });
   if (g_fail) return MQ_OK;
+  std::vector<int64_t> p_src;   // the tape behind each P descriptor
   for (int64_t i = 0; i < nq; i++) {
     const int k = kind_of[i];
     if (k == 2) continue;
@@ -4192,7 +4248,36 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
     words[k].insert(words[k].end(), t.begin(), t.end());
     ds[k].push_back(d);
     temps[k] = std::max(temps[k], qsa_temps(T->qct[i], k));
+    if (k == 0) p_src.push_back(i);
   }
+  // low-limb prefilter programs of the P tapes, behind P's programs (the histograms above stay
+  // those of the tapes' own programs); pf_ds parallel to ds[0]
+  std::vector<GDesc> pf_ds(ds[0].size());
+  std::vector<uint32_t> pf_static((ds[0].size() + 31) / 32 + 1, 0u);
+  T->pf_count = 0;
+  T->pf_tape.clear();
+  T->pf_has.clear();
+  T->pf_words = (int)((ds[0].size() + 31) / 32);
+  for (size_t j = 0; j < ds[0].size(); j++) {
+    const CompiledTape& x = T->qct[p_src[j]];
+    GDesc d = ds[0][j];
+    d.prog_off = 0;
+    d.prog_len = 0;
+    std::vector<uint32_t> t;
+    if (!x.prog_pf.empty() && qsa_translate_pf(c, x, t)) {
+      d.prog_off = (uint32_t)words[0].size();
+      d.prog_len = (uint32_t)t.size();
+      d.alg_ops = (uint32_t)std::llround(x.pf_alg_ops);
+      words[0].insert(words[0].end(), t.begin(), t.end());
+      T->pf_count++;
+    } else {
+      pf_static[j >> 5] |= 1u << (j & 31);
+    }
+    pf_ds[j] = d;
+    T->pf_tape.push_back((int32_t)d.tape);
+    T->pf_has.push_back(d.prog_len ? 1 : 0);
+  }
+  if (pf_ds.empty()) pf_ds.push_back(GDesc{});
   // [P programs | END END | G programs | END END]: the dispatch tail prefetches one word past
   // each program's END
   pt.reset(new PhaseTimer(&c->host_t[5]));
@@ -4230,6 +4315,8 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   UploadPack pk;
   pk.add(T->qdescs, descs.data(), descs.size());
   pk.add(T->qprog, prog.data(), prog.size());
+  pk.add(T->pf_descs, pf_ds.data(), pf_ds.size());
+  pk.add(T->pf_static, pf_static.data(), pf_static.size());
   if (T->fca) {
     T->fc_count = (int)fap.tape_out.size();
     T->fca_atoms = (int)fap.atoms.size();
@@ -4274,7 +4361,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   }
   // (translated programs, descriptors, flat-kernel tables and staging rows: one copy)
   HIPCHK(pk.commit(T->pack1, c->stream, c->stage));
-  T->qargs_valid[0] = T->qargs_valid[1] = false;
+  T->qargs_valid[0] = T->qargs_valid[1] = T->qargs_valid[2] = false;
   T->qsa_live = true;
   return MQ_OK;
 }
@@ -4523,8 +4610,17 @@ static int refresh_wide_unsupported(mq_ctx* c, mq_tapes* T, hipStream_t st) {
   return MQ_OK;
 }
 
+// Low-limb prefilter launch (launch_all): on from this many models of a device's shard (a smaller
+// launch keeps the parent's kernels, programs and counters), and its target workgroup count
+// (2 048-model tiles x tape groups; MQ_PF_WG overrides).  C2, ms a step at 512 / 1k / 2k / 4k / 8k /
+// 16k / 32k workgroups: 1.34 / 1.13 / 0.91 / 0.81 / 0.79 / 0.79 / 0.80 (profiles/pf01/sweep): finer
+// groups shorten the last round of workgroups until the preload per group shows
+constexpr int64_t kPfMinModels = 4096;
+constexpr int64_t kPfWorkgroups = 16384;
+
 static int launch_all(mq_ctx* c, mq_tapes* T, int32_t* best, uint8_t* verdicts, hipStream_t st) {
   T->in_flight = true;   // (cleared where the host waits for the launch: mq_tapes_free skips its sync)
+  T->pf_ran = false;
   if (const int rc = refresh_wide_unsupported(c, T, st)) return rc;
   bool use_qsa = c->qsa_ready && c->use_asm && T->qsa.count > 0;
   // latency-bound launch (a few tapes over a few models): G runs one tape per wave instead of
@@ -4930,6 +5026,44 @@ static int launch_all(mq_ctx* c, mq_tapes* T, int32_t* best, uint8_t* verdicts, 
     q.n_bool_masks = (uint32_t)c->n_bmask;
     if (k == 1) q.prof_out = prof_buffer(c, -1);
     size_t lds = (size_t)q.lds_wave_bytes * 4 + (size_t)q.n_stage * 256 + (k == 1 ? 4 * (size_t)kQsaProfBytes : 0);
+    // Low-limb prefilter in front of P (first-hit mode, throughput launches): the bitmap is
+    // cleared, the mode-4 launch sets the (block, tape) pairs its narrow programs leave alive,
+    // and P runs only those (and the tapes without a prefilter program).  Below kPfMinModels
+    // models the launch is the unfiltered one (MQ_PREFILTER=force lifts that, =0 turns it off).
+    const bool pf_on = k == 0 && !verdicts && !latency && T->pf_count > 0 && prefilter_enabled() &&
+                       (c->M >= kPfMinModels || prefilter_forced());
+    if (k == 0) T->pf_ran = pf_on;
+    if (pf_on) {
+      const int64_t rows = (c->M + 63) / 64;
+      const size_t bytes = (size_t)rows * (size_t)T->pf_words * sizeof(uint32_t);
+      HIPCHK(T->pf_alive.ensure(bytes));
+      T->pf_rows = rows;
+      const int64_t tiles2k = (c->M + 2047) / 2048;
+      int64_t pf_wg = kPfWorkgroups;   // target workgroup count (MQ_PF_WG overrides)
+      if (const char* e = std::getenv("MQ_PF_WG")) pf_wg = std::max(1L, std::atol(e));
+      int64_t ptpg = (int64_t(n) * tiles2k + pf_wg - 1) / pf_wg;
+      ptpg = std::max<int64_t>(1, std::min<int64_t>(ptpg, n));
+      const int64_t pgy = std::min<int64_t>((n + ptpg - 1) / ptpg, 65535);
+      ptpg = (n + pgy - 1) / pgy;
+      q.alive = T->pf_alive.as<uint32_t>();
+      q.alive_static = T->pf_static.as<uint32_t>();
+      q.pf_descs = T->pf_descs.p;
+      q.alive_words = (uint32_t)T->pf_words;
+      QArgs qp = q;
+      qp.mode = 4u;
+      qp.tapes_per_group = (uint32_t)ptpg;
+      qp.lds_wave_bytes = 0;
+      if (!T->qargs_valid[2] || std::memcmp(&T->qargs_dev_copy[2], &qp, sizeof(QArgs)) != 0) {
+        void* h = c->stage.put(&qp, sizeof(QArgs), st);
+        if (!h) return MQ_ERR_NOMEM;
+        HIPCHK(hipMemcpyAsync(T->qargs[2].p, h, sizeof(QArgs), hipMemcpyHostToDevice, st));
+        T->qargs_dev_copy[2] = qp;
+        T->qargs_valid[2] = true;
+      }
+      HIPCHK(start_timer());
+      HIPCHK(hipMemsetAsync(T->pf_alive.p, 0, bytes, st));
+      HIPCHK(launch_qsa(0, T->qargs[2].as<QArgs>(), (unsigned)tiles2k, (unsigned)((n + ptpg - 1) / ptpg), 0, st));
+    }
     // the argument block only changes with the output buffer / mode / models: re-upload then
     if (!T->qargs_valid[k] || std::memcmp(&T->qargs_dev_copy[k], &q, sizeof(QArgs)) != 0) {
       PhaseTimer pq(&c->host_t[6]);
@@ -5380,6 +5514,50 @@ int mq_tapes_qsa_split(mq_tapes* T, int32_t* n_p, int32_t* n_g, int32_t* live) {
   if (n_p) *n_p = T->qsa_live ? T->q_count[0] : 0;
   if (n_g) *n_g = T->qsa_live ? T->q_count[1] : 0;
   if (live) *live = T->qsa_live ? 1 : 0;
+  return MQ_OK;
+}
+
+int mq_tapes_prefilter_split(mq_tapes* T, int32_t* n_prefiltered, int32_t* ran) {
+  if (!T) return MQ_ERR_ARG;
+  if (n_prefiltered) *n_prefiltered = T->qsa_live ? T->pf_count : 0;
+  if (ran) *ran = (T->qsa_live && T->pf_ran) ? 1 : 0;
+  return MQ_OK;
+}
+
+int mq_tapes_prefilter_alive(mq_tapes* T, uint32_t* words, int64_t cap_words, int64_t* rows, int32_t* words_per_row,
+                             int32_t* desc_tape, uint8_t* desc_has, int32_t cap_desc, int32_t* n_desc) {
+  if (!T || !T->ctx) return MQ_ERR_ARG;
+  mq_ctx* c = T->ctx;
+  const bool ran = T->qsa_live && T->pf_ran;
+  const int64_t r = ran ? T->pf_rows : 0;
+  const int64_t total = r * T->pf_words;
+  if (rows) *rows = r;
+  if (words_per_row) *words_per_row = ran ? T->pf_words : 0;
+  if (n_desc) *n_desc = ran ? (int32_t)T->pf_tape.size() : 0;
+  if (!ran) return MQ_OK;
+  if (desc_tape && desc_has && cap_desc >= (int32_t)T->pf_tape.size()) {
+    std::memcpy(desc_tape, T->pf_tape.data(), T->pf_tape.size() * sizeof(int32_t));
+    std::memcpy(desc_has, T->pf_has.data(), T->pf_has.size());
+  }
+  if (words && cap_words >= total && total > 0) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());   // (a diagnostic read: whichever stream the launch used)
+    HIPCHK(hipMemcpy(words, T->pf_alive.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  return MQ_OK;
+}
+
+int mq_tape_prefilter_program(const mq_tape_batch* tb, int32_t t, uint32_t* words, int32_t cap, int32_t* n_words,
+                              double* pf_alg_ops, int32_t* depth) {
+  if (!tb || t < 0 || t >= tb->n_tapes || !n_words) return MQ_ERR_ARG;
+  CompileLimits lim;
+  CompiledTape c = compile_tape(tb, t, lim);
+  if (!c.supported) return MQ_ERR_TAPE;
+  *n_words = (int32_t)c.prog_pf.size();
+  if (words && cap >= (int32_t)c.prog_pf.size() && !c.prog_pf.empty())
+    std::memcpy(words, c.prog_pf.data(), c.prog_pf.size() * sizeof(uint32_t));
+  if (pf_alg_ops) *pf_alg_ops = c.pf_alg_ops;
+  if (depth) *depth = c.depth_pf;
   return MQ_OK;
 }
 

@@ -97,6 +97,16 @@ struct QArgs {
   uint32_t reserved_1a4;         // 0x1a4 (unused; keeps the layout the generated code addresses)
   unsigned long long* prof_out;  // 0x1a8 G profile build only: (cycles, count) per handler kind
   const uint32_t* dense_words;   // 0x1b0 G: dense lookup slots (FuncDev dense_base / dense_e)
+  // P, low-limb prefilter (gen_qsa.py pf_frame / alive_scan).  alive: [ceil(M / 64)][alive_words]
+  // bits, bit (desc & 31) of word desc >> 5 of a block's row = "tape desc may hold for a model of
+  // the block".  Mode 4 sets the bits of the blocks its narrow programs do not clear; mode 0 with
+  // a non-null alive runs, per 64-model block, only the tapes whose bit is set there or in
+  // alive_static (the descriptors without a prefilter program).  Null: the launch is unfiltered.
+  uint32_t* alive;               // 0x1b8
+  const uint32_t* alive_static;  // 0x1c0 [alive_words]
+  const void* pf_descs;          // 0x1c8 mode 4: GDesc[] parallel to descs (prog_len 0: no prefilter)
+  uint32_t alive_words;          // 0x1d0
+  uint32_t reserved_1d4;         // 0x1d4
 };
 static_assert(sizeof(void*) == 8, "64-bit");
 static_assert(__builtin_offsetof(QArgs, M) == 0x40, "QArgs layout");
@@ -111,6 +121,10 @@ static_assert(__builtin_offsetof(QArgs, n_bool_masks) == 0x1a0, "QArgs layout");
 static_assert(__builtin_offsetof(QArgs, reserved_1a4) == 0x1a4, "QArgs layout");
 static_assert(__builtin_offsetof(QArgs, prof_out) == 0x1a8, "QArgs layout");
 static_assert(__builtin_offsetof(QArgs, dense_words) == 0x1b0, "QArgs layout");
+static_assert(__builtin_offsetof(QArgs, alive) == 0x1b8, "QArgs layout");
+static_assert(__builtin_offsetof(QArgs, alive_static) == 0x1c0, "QArgs layout");
+static_assert(__builtin_offsetof(QArgs, pf_descs) == 0x1c8, "QArgs layout");
+static_assert(__builtin_offsetof(QArgs, alive_words) == 0x1d0, "QArgs layout");
 
 // variant 0 = P (preloaded variables, qsa_kernel), 1 = G (general, qsg_kernel)
 hipError_t launch_qsa(int variant, const QArgs* d_args, unsigned gx, unsigned gy, size_t lds, hipStream_t st);

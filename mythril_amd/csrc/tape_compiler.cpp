@@ -119,7 +119,217 @@ struct Fail {
   std::string why;
 };
 
+// Low-limb prefilter (gprog.h PfOp).  For ADD / SUB / NEG / MUL and the bitwise ops the low 32
+// bits of the result depend only on the low 32 bits of the operands, so an EQ conjunct of the
+// root conjunction whose cone holds nothing else can be tested at one limb: a mismatch there
+// proves the conjunct, and with it the tape, false.  Every node of the cone is classified in
+// index order (kids precede their users): ineligible, a value, or a constant (folded at 32
+// bits).  The cheapest eligible EQ (§8(d) cost at L = 1, ties to the first written) that fits
+// kPfMaxDepth slots and kPfMaxInstr instructions becomes the program; shared sub-terms are
+// re-evaluated inline (no temps), operands in Sethi-Ullman order.
+struct PfBuilder {
+  enum { BAD = 0, VAL = 1, KONST = 2 };
+  const std::vector<INode>& N;
+  const std::vector<uint32_t>& consts;
+  std::vector<char> st;
+  std::vector<uint32_t> kv;
+  std::vector<int> need, len;
+  std::vector<double> cost;
+  std::vector<uint32_t> prog;
+  int maxd = 0;
+
+  PfBuilder(const std::vector<INode>& nodes, const std::vector<uint32_t>& c) : N(nodes), consts(c) {}
+
+  static uint32_t fold(uint32_t g, uint32_t a, uint32_t b) {
+    switch (g) {
+      case G_ADD: return a + b;
+      case G_SUB: return a - b;
+      case G_MUL: return a * b;
+      case G_BAND: return a & b;
+      case G_BOR: return a | b;
+      case G_BXOR: return a ^ b;
+      case G_NEG: return 0u - a;
+      default: return ~a;   // G_BNOT
+    }
+  }
+  // (len, need, cost) of "a OP b" with both operands on the stack / one of them a constant
+  void binary(int x, int a, int b, bool sub) {
+    const int cap = 1 << 20;
+    if (st[a] == VAL && st[b] == VAL) {
+      const bool sw = need[b] > need[a];
+      need[x] = sw ? std::max(need[b], need[a] + 1) : std::max(need[a], need[b] + 1);
+      len[x] = std::min(cap, len[a] + len[b] + 1 + (sub && sw ? 1 : 0));
+      cost[x] = cost[a] + cost[b] + (sub && sw ? 1 : 0);
+    } else {
+      const int v = st[a] == VAL ? a : b;
+      const bool neg = sub && v == b;   // k - x = -x + k
+      need[x] = need[v];
+      len[x] = std::min(cap, len[v] + 1 + (neg ? 1 : 0));
+      cost[x] = cost[v] + (neg ? 1 : 0);
+    }
+  }
+  void classify(int var_limit) {
+    const int NI = (int)N.size();
+    st.assign(NI, BAD);
+    kv.assign(NI, 0);
+    need.assign(NI, 1);
+    len.assign(NI, 1);
+    cost.assign(NI, 0.0);
+    for (int x = 0; x < NI; x++) {
+      const INode& n = N[x];
+      if (n.width < 32) continue;
+      switch (n.gop) {
+        case G_PUSH_VAR:
+          if (n.leaf && n.imm < (uint32_t)var_limit) st[x] = VAL;
+          break;
+        case G_PUSH_CONST:
+          if (n.leaf && n.imm < consts.size()) {
+            st[x] = KONST;
+            kv[x] = consts[n.imm];
+          }
+          break;
+        case G_NEG: case G_BNOT: {
+          const int a = n.kid[0];
+          if (n.nk != 1 || st[a] == BAD) break;
+          if (st[a] == KONST) {
+            st[x] = KONST;
+            kv[x] = fold(n.gop, kv[a], 0);
+          } else {
+            st[x] = VAL;
+            need[x] = need[a];
+            len[x] = len[a] + 1;
+            cost[x] = cost[a] + 1;
+          }
+          break;
+        }
+        case G_ADD: case G_SUB: case G_MUL: case G_BAND: case G_BOR: case G_BXOR: {
+          const int a = n.kid[0], b = n.kid[1];
+          if (n.nk != 2 || st[a] == BAD || st[b] == BAD) break;
+          const bool zero = (n.gop == G_MUL || n.gop == G_BAND) &&
+                            ((st[a] == KONST && kv[a] == 0) || (st[b] == KONST && kv[b] == 0));
+          if (zero || (st[a] == KONST && st[b] == KONST)) {
+            st[x] = KONST;
+            kv[x] = zero ? 0u : fold(n.gop, kv[a], kv[b]);
+          } else {
+            st[x] = VAL;
+            binary(x, a, b, n.gop == G_SUB);
+            cost[x] += n.gop == G_MUL ? 2 : 1;
+          }
+          break;
+        }
+        default:
+          break;
+      }
+    }
+  }
+  void put(uint32_t op, int d, uint32_t imm) {
+    prog.push_back(pfword(op, (uint32_t)d));
+    prog.push_back(imm);
+    maxd = std::max(maxd, d + 1);
+  }
+  static uint32_t op_of(uint32_t g, bool k) {
+    switch (g) {
+      case G_ADD: return k ? PF_ADDK : PF_ADD;
+      case G_SUB: return k ? PF_ADDK : PF_SUB;
+      case G_MUL: return k ? PF_MULK : PF_MUL;
+      case G_BAND: return k ? PF_ANDK : PF_BAND;
+      case G_BOR: return k ? PF_ORK : PF_BOR;
+      case G_BXOR: return k ? PF_XORK : PF_BXOR;
+      case G_NEG: return PF_NEG;
+      case G_BNOT: return PF_BNOT;
+      default: return k ? PF_EQK : PF_EQ;
+    }
+  }
+  // "a OP b" at slot d (OP = the node's, or the final EQ)
+  void emit_binary(uint32_t g, int a, int b, int d) {
+    const bool sub = g == G_SUB;
+    if (st[a] == VAL && st[b] == VAL) {
+      if (need[b] > need[a]) {
+        emit(b, d);
+        emit(a, d + 1);
+        put(op_of(g, false), d + 1, 0);
+        if (sub) put(PF_NEG, d, 0);   // b - a -> a - b
+      } else {
+        emit(a, d);
+        emit(b, d + 1);
+        put(op_of(g, false), d + 1, 0);
+      }
+    } else if (st[b] == KONST) {
+      emit(a, d);
+      put(op_of(g, true), d, sub ? 0u - kv[b] : kv[b]);
+    } else {
+      emit(b, d);
+      if (sub) put(PF_NEG, d, 0);
+      put(op_of(g, true), d, kv[a]);
+    }
+  }
+  void emit(int x, int d) {
+    const INode& n = N[x];
+    if (st[x] == KONST) put(PF_PUSH_K, d, kv[x]);
+    else if (n.gop == G_PUSH_VAR) put(PF_PUSH_VAR, d, n.imm);
+    else if (n.nk == 1) {
+      emit(n.kid[0], d);
+      put(op_of(n.gop, false), d, 0);
+    } else emit_binary(n.gop, n.kid[0], n.kid[1], d);
+  }
+};
+
 }  // namespace
+
+bool prefilter_enabled() {
+  const char* e = std::getenv("MQ_PREFILTER");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
+bool prefilter_forced() {
+  const char* e = std::getenv("MQ_PREFILTER");
+  return e && std::string(e) == "force";
+}
+
+// The prefilter program of the internal DAG `nodes` with root `root` (a verdict tape), if any.
+static void build_prefilter(const std::vector<INode>& nodes, int root, int var_limit, CompiledTape& out) {
+  if (nodes[root].leaf || nodes[root].gop != G_AND) return;
+  std::vector<int> conj, stack{root};
+  while (!stack.empty()) {   // conjuncts left to right
+    const int y = stack.back();
+    stack.pop_back();
+    if (!nodes[y].leaf && nodes[y].gop == G_AND && nodes[y].nk == 2) {
+      stack.push_back(nodes[y].kid[1]);
+      stack.push_back(nodes[y].kid[0]);
+    } else {
+      conj.push_back(y);
+    }
+  }
+  PfBuilder pb(nodes, out.consts);
+  pb.classify(var_limit);
+  int best = -1;
+  double best_cost = 0;
+  for (int c : conj) {
+    const INode& n = nodes[c];
+    if (n.leaf || n.gop != G_EQ || n.nk != 2 || n.imm < 32) continue;
+    const int a = n.kid[0], b = n.kid[1];
+    if (pb.st[a] == PfBuilder::BAD || pb.st[b] == PfBuilder::BAD) continue;
+    int len, need;
+    double cost;
+    if (pb.st[a] == PfBuilder::KONST && pb.st[b] == PfBuilder::KONST) {
+      if (pb.kv[a] == pb.kv[b]) continue;   // folds to true at 32 bits: proves nothing
+      len = 2, need = 1, cost = 1;
+    } else {
+      pb.binary(c, a, b, false);
+      len = pb.len[c], need = pb.need[c], cost = pb.cost[c] + 1;
+    }
+    if (len > kPfMaxInstr || need > kPfMaxDepth) continue;
+    if (best < 0 || cost < best_cost) best = c, best_cost = cost;
+  }
+  if (best < 0) return;
+  pb.emit_binary(G_EQ, nodes[best].kid[0], nodes[best].kid[1], 0);
+  pb.put(PF_END, 0, 0);
+  double ops = 0;
+  for (size_t i = 0; i < pb.prog.size(); i += 2) ops += pf_op_cost(pb.prog[i] & 0xFFu);
+  out.prog_pf = std::move(pb.prog);
+  out.depth_pf = pb.maxd;
+  out.pf_alg_ops = ops;
+}
 
 static double node_alg_ops(const mq_node* nd, int64_t i);
 
@@ -724,8 +934,12 @@ CompiledTape compile_tape(const mq_tape_batch* batch, int32_t t, const CompileLi
         out.n_temps_g = 0;
       }
     }
+    // low-limb prefilter of a verdict tape (only the P interpreter runs it: its preloaded variables)
+    if (!lim.value_root && std::getenv("MQ_NO_BAIL") == nullptr && prefilter_enabled())
+      build_prefilter(B.nodes, root, lim.bail_var_limit, out);
     out.supported = true;
   } catch (const Fail& f) {
+    out.prog_pf.clear();
     out.supported = false;
     out.why = f.why;
     out.prog.clear();

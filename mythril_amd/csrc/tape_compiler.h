@@ -47,7 +47,18 @@ struct CompiledTape {
   uint32_t n_nodes = 0;          // DAG size of the boundary tape (metric)
   std::vector<uint32_t> wide_funcs;   // functions looked up by a chunked wide key (MQ_OP_UF_WIDE)
   double alg_ops = 0;            // SURVEY §8(d) algorithmic cost per model
+  // low-limb prefilter (gprog.h PfOp): the cheapest eligible EQ conjunct of a verdict tape's root
+  // conjunction at 32 bits, PF_END-terminated; empty when the tape has none (or MQ_PREFILTER=0 /
+  // MQ_NO_BAIL=1).  pf_alg_ops = its §8(d) cost at L = 1
+  std::vector<uint32_t> prog_pf;
+  int depth_pf = 0;
+  double pf_alg_ops = 0;
 };
+
+// MQ_PREFILTER (read per call: tests flip it): "0" = no prefilter programs and no prefilter
+// launch; "force" = the launch ignores its model-count gate; anything else / unset = default.
+bool prefilter_enabled();
+bool prefilter_forced();
 
 struct CompileLimits {
   // LDS operand stack per wave: depth x L x 256 B (L = 8: 2 KB, 16: 4 KB, 32: 8 KB, 64: 16 KB

@@ -88,7 +88,12 @@ def load_library(path: str = LIB_PATH):
         L.mq_tape_compile_info_g.argtypes = [C.POINTER(MqTapeBatch), C.c_int32] + [C.POINTER(C.c_int32)] * 3
         L.mq_tape_program.argtypes = [C.POINTER(MqTapeBatch), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_int32)]
         L.mq_tape_program_g.argtypes = [C.POINTER(MqTapeBatch), C.c_int32, C.POINTER(C.c_uint32), C.c_int32] + [C.POINTER(C.c_int32)] * 4
-        L.mq_tapes_upload_dag.argtypes = [P, C.POINTER(MqDagBatch), C.POINTER(P), C.POINTER(C.c_int32)]
+        L.mq_tape_prefilter_program.argtypes = [C.POINTER(MqTapeBatch), C.c_int32, C.POINTER(C.c_uint32), C.c_int32,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.mq_tapes_prefilter_split.argtypes = [P] + [C.POINTER(C.c_int32)] * 2
+        L.mq_tapes_prefilter_alive.argtypes = [P, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int32)]
+        L.mq_tapes_upload_dag.argtypes =[P, C.POINTER(MqDagBatch), C.POINTER(P), C.POINTER(C.c_int32)]
         L.mq_dag_expand.argtypes = [C.POINTER(MqDagBatch), C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]
         L.mq_models_shard.argtypes = [C.POINTER(MqModelBatch), C.c_int64, C.c_int64, C.POINTER(MqModelBatch), C.POINTER(P)]
         L.mq_models_shard_free.argtypes = [P]
@@ -191,6 +196,21 @@ def tape_program_g(tb: TapeBatch, t: int):
     _check(L.mq_tape_program_g(C.byref(s), t, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n),
                                C.byref(d), C.byref(nt), C.byref(sp)), "tape_program_g")
     return out, d.value, nt.value, bool(sp.value)
+
+
+def tape_prefilter_program(tb: TapeBatch, t: int):
+    """Host-only: the low-limb prefilter program of tape t (``mq_tape_prefilter_program``; gprog.h
+    PfOp, two words an instruction: op | slot << 8, then a 32-bit immediate) and its §8(d) cost at
+    one limb: (words, pf_alg_ops, depth).  No program (no eligible EQ conjunct, MQ_PREFILTER=0,
+    MQ_NO_BAIL=1): an empty array."""
+    L = load_library()
+    s, keep = as_tape_batch(tb)
+    n, d, ops = C.c_int32(), C.c_int32(), C.c_double()
+    _check(L.mq_tape_prefilter_program(C.byref(s), t, None, 0, C.byref(n), None, None), "tape_prefilter_program")
+    out = np.zeros(n.value, np.uint32)
+    _check(L.mq_tape_prefilter_program(C.byref(s), t, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n),
+                                       C.byref(ops), C.byref(d)), "tape_prefilter_program")
+    return out, ops.value, d.value
 
 
 def shard_models(mb: ModelBatch, lo: int, hi: int) -> ModelBatch:
@@ -347,6 +367,35 @@ class CompiledTapes:
             return h
         pr = pr.reshape(k, k)
         return h, {(names[i], names[j]): int(pr[i, j]) for i, j in zip(*np.nonzero(pr))}
+
+    def prefilter_split(self):
+        """(tapes on the P interpreter with a low-limb prefilter program, whether the last
+        first-hit launch ran the prefilter in front of P) (mq_tapes_prefilter_split)."""
+        n, ran = C.c_int32(), C.c_int32()
+        _check(self.ev.lib.mq_tapes_prefilter_split(self.handle, C.byref(n), C.byref(ran)), "mq_tapes_prefilter_split")
+        return n.value, bool(ran.value)
+
+    def prefilter_alive(self):
+        """Diagnostic, after a launch that ran the prefilter: (bits, tapes, has) -- bits[b, d]
+        True where P descriptor d stayed alive for the 64-model block b of the lead device's
+        shard, tapes[d] the descriptor's tape, has[d] whether it has a prefilter program (the
+        others' bits are never set: P runs them everywhere).  None when it did not run."""
+        lib = self.ev.lib
+        rows, wpr, nd = C.c_int64(), C.c_int32(), C.c_int32()
+        _check(lib.mq_tapes_prefilter_alive(self.handle, None, 0, C.byref(rows), C.byref(wpr), None, None, 0, C.byref(nd)),
+               "mq_tapes_prefilter_alive")
+        if rows.value == 0:
+            return None
+        words = np.zeros(max(1, rows.value * wpr.value), np.uint32)
+        tapes = np.zeros(max(1, nd.value), np.int32)
+        has = np.zeros(max(1, nd.value), np.uint8)
+        _check(lib.mq_tapes_prefilter_alive(self.handle, words.ctypes.data_as(C.POINTER(C.c_uint32)), words.size, C.byref(rows),
+                                            C.byref(wpr), tapes.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            has.ctypes.data_as(C.POINTER(C.c_uint8)), nd.value, C.byref(nd)),
+               "mq_tapes_prefilter_alive")
+        w = words[:rows.value * wpr.value].reshape(rows.value, wpr.value)
+        bits = ((w[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & 1).astype(bool)
+        return bits.reshape(rows.value, wpr.value * 32)[:, :nd.value], tapes[:nd.value], has[:nd.value].astype(bool)
 
     def free(self) -> None:
         if self.handle:
