@@ -3,6 +3,9 @@
 // Host side of the quick-sat evaluator: owns the device copies of the candidate models
 // (ModelCache contents, mythril/support/support_utils.py:56-58), compiles boundary tapes into
 // GPU stack programs (tape_compiler.cpp) and launches the gfx950 kernels (qs_kernels.hip).
+// The host planners -- the threaded-code translator (qsa_translate.cpp) and the flat-conjunction
+// planners (fc_plan.cpp) -- are host-only files: they see the context's QsaTable and ModelLayout
+// views, never the context.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -28,6 +31,8 @@
 #include "gprog.h"
 #include "qs_launch.h"
 #include "qsa_table.h"
+#include "qsa_translate.h"
+#include "fc_plan.h"
 #include "tape_compiler.h"
 #include "host_keccak.h"
 
@@ -308,13 +313,9 @@ struct UploadPack {
 
 }  // namespace
 
-// words past the function entries that reads may touch (8 entries of the widest G table)
-static constexpr size_t kEntryPadWords = 512;
 // most entry slots per model a function may have to get dense lookup slots (FuncDev dense_e)
 static constexpr int64_t kDenseMaxE = 16;
 
-// the assembly interpreter keeps temps in LDS (2 KB per temp per wave, 4 waves per workgroup)
-static constexpr int kQsaMaxTemps = 16;
 // by default bail points (gprog.h G_BAIL) go on the tapes whose variables P preloads: only P takes
 // them unless MQ_G_BAIL=1 lifts the limit (tape_compiler.h g_bail_enabled)
 static_assert(CompileLimits{}.bail_var_limit == kQsaVars, "by default bail points are for the tapes P can run");
@@ -362,9 +363,7 @@ struct mq_ctx {
   // models
   int64_t M = 0, index_base = 0;
   int n_vars = 0, n_funcs = 0;
-  std::vector<uint16_t> var_width;
   DevBuf vars, var_off, var_nl, funcs, entry_ptr, entry_words, else_words, dense_words;
-  int64_t entry_words_n = 0;   // words of function entries (G scans them with 32-bit offsets)
   DevBuf counters;
   DevBuf best_tmp;  // scratch first-hit buffer for the synchronous API
   DevBuf scratch;   // per-wave temp slots of the HIP C++ interpreter (persistent grid)
@@ -383,9 +382,8 @@ struct mq_ctx {
   uint64_t table_uploads = 0;   // derived-table uploads taken
   std::vector<FuncDev> funcs_dev_h;   // host copy of `funcs` (mq_models_download_funcs)
   int64_t else_words_n = 0, dense_words_n = 0;
-  // Bool variables as packed lane masks [tile][n_bmask] (G kernel PUSH_PKB): bmask_of_var[v] =
-  // mask index of Bool variable v (-1: none); bmask_rows[j] = its variable row
-  std::vector<int32_t> bmask_of_var;
+  // Bool variables as packed lane masks [tile][n_bmask] (G kernel PUSH_PKB): layout.bmask_of_var[v]
+  // = mask index of Bool variable v (-1: none); bmask_rows[j] = its variable row
   int32_t n_bmask = 0;
   DevBuf bmasks, bmask_rows;
   DevBuf prof;   // G profile build (kQsaProfBytes > 0): per-kind (cycles, count), mq_qsa_profile
@@ -395,21 +393,15 @@ struct mq_ctx {
   PinnedBuf readback_host;  // a first-hit launch's counter slots and first hits
   StageRing stage;          // small uploads (DevBuf::upload_staged)
   hipEvent_t stage_ev = nullptr;   // a launch on a caller's stream waits for the context stream's copies
-  // assembly interpreters (qsa.hip): handler byte offsets read back at context creation;
-  // k = 0 the P kernel (preloaded variables), k = 1 the G kernel (general)
+  // assembly interpreters (qsa.hip): the handler table, its byte offsets read back at context
+  // creation; k = 0 the P kernel (preloaded variables), k = 1 the G kernel (general)
   bool qsa_ready = false;
-  std::vector<uint32_t> qsa_off[2];
-  int qsa_index[2][QK_COUNT][kQsaStack][kQsaSel + 1];
-  // G kinds that wait for every vector load themselves (PUSH_MEMB, MEQK*, UF1*)
-  bool qsa_vm_drain[QK_COUNT] = {};
+  QsaTable qsa;
   uint32_t qsa_var_row[64];
-  std::vector<uint8_t> qsa_data_words;
-  uint32_t qsa_hbase_lo[2] = {0, 0};   // low 32 bits of each interpreter's handler base
-  std::vector<int16_t> qsa_kind_of[2];  // handler byte offset / 4 -> QsaKind (histograms)
   DevBuf qsa_args;
-  // host copies of the model batch layout the QSA translation depends on
-  std::vector<uint32_t> var_off_h, var_nl_h;
-  std::vector<mq_func_desc> funcs_h;
+  // host copy of the model batch layout the translations and flat plans depend on (the host
+  // planners see these two views, never the context: qsa_translate.h, fc_plan.h)
+  ModelLayout layout;
   uint64_t models_gen = 0;      // bumped by every mq_models_upload
   // bumped by an upload whose layout differs from the previous batch's (variables and their
   // widths, Bool lane-mask indices, function signatures): the tape translations, column plans and
@@ -441,10 +433,6 @@ struct mq_ctx {
   std::vector<ncclComm_t> comms;
   std::vector<int64_t> shard_lo;
   int64_t M_total = 0;
-};
-
-struct FcaPlanSeg {   // one fca_kernel launch (fca_plan)
-  int atom_off, n_atoms, group_off, n_groups, tape_first, n_tapes, chunk_first, smask_off, n_smask;
 };
 
 struct mq_tapes {
@@ -829,21 +817,13 @@ const char* mq_strerror(int code) {
   }
 }
 
-// Handler byte offset -> the 16-bit word field that encodes it: P / G handlers are 4-byte
-// aligned (shift 2); the diagnostic G profile build aligns them to 8 bytes (shift 3, 512 KB reach)
-static inline uint32_t hword(int k, uint32_t off) { return off >> (k == 1 ? kQsaHandlerShiftG : 2); }
-
-// Read back the byte offset of every handler of the assembly interpreters (kernel mode 2).
+// Read back the byte offset of every handler of the assembly interpreters (kernel mode 2);
+// QsaTable::build makes the table of them.
 static int qsa_init(mq_ctx* c) {
-  bool ok = true;
+  std::vector<uint32_t> off[2];
+  uint32_t base_lo[2] = {0, 0};
   for (int k = 0; k < 2; k++) {
     const int nh = k == 0 ? kQsaHandlersP : kQsaHandlersG;
-    static_assert(kQsaStackP <= kQsaStack && kQsaStackG <= kQsaStack, "qsa_index holds both stacks");
-    const QsaHandlerKey* keys = k == 0 ? kQsaHandlerKeysP : kQsaHandlerKeysG;
-    for (int q = 0; q < QK_COUNT; q++)
-      for (int d = 0; d < kQsaStack; d++)
-        for (int v = 0; v <= kQsaSel; v++) c->qsa_index[k][q][d][v] = -1;
-    for (int h = 0; h < nh; h++) c->qsa_index[k][keys[h].kind][keys[h].d < 0 ? 0 : keys[h].d][keys[h].v + 1] = h;
     DevBuf table;   // nh handler offsets, then the absolute handler base (lo, hi)
     HIPCHK(table.ensure(sizeof(uint32_t) * (nh + 2)));
     HIPCHK(hipMemsetAsync(table.p, 0xFF, sizeof(uint32_t) * (nh + 2), c->stream));
@@ -852,33 +832,13 @@ static int qsa_init(mq_ctx* c) {
     qa.mode = 2;
     HIPCHK(c->qsa_args.upload(&qa, 1, c->stream));
     HIPCHK(launch_qsa(k, c->qsa_args.as<QArgs>(), 1, 1, 0, c->stream));
-    c->qsa_off[k].resize(nh + 2);
-    HIPCHK(hipMemcpyAsync(c->qsa_off[k].data(), table.p, sizeof(uint32_t) * (nh + 2), hipMemcpyDeviceToHost, c->stream));
+    off[k].resize(nh + 2);
+    HIPCHK(hipMemcpyAsync(off[k].data(), table.p, sizeof(uint32_t) * (nh + 2), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->qsa_hbase_lo[k] = c->qsa_off[k][nh];
-    c->qsa_kind_of[k].assign(1 << 16, -1);
-    for (int h = 0; h < nh; h++)
-      if (hword(k, c->qsa_off[k][h]) < (1u << 16)) c->qsa_kind_of[k][hword(k, c->qsa_off[k][h])] = (int16_t)keys[h].kind;
-    uint32_t max_off = 0;
-    for (int h = 0; h < nh; h++) {
-      ok = ok && c->qsa_off[k][h] != 0xFFFFFFFFu && hword(k, c->qsa_off[k][h]) < (1u << 16) &&
-           (c->qsa_off[k][h] & ((k == 1 ? (1u << kQsaHandlerShiftG) : 4u) - 1)) == 0;
-      max_off = std::max(max_off, c->qsa_off[k][h]);
-    }
-    // P program entries and G's decoded program window hold the low 32 bits of absolute handler
-    // addresses: they must share the high half (the kernels keep it in s19)
-    ok = ok && (uint64_t)c->qsa_hbase_lo[k] + max_off < (1ull << 32);
-    c->qsa_off[k].resize(nh);
+    base_lo[k] = off[k][nh];
+    off[k].resize(nh);
   }
-  // G handler word index -> inline data words that follow it (generated: the window words the
-  // handler body reads, gen_qsa.py handler_data_words)
-  c->qsa_data_words.assign(1 << 16, 0);
-  for (int h = 0; ok && h < kQsaHandlersG; h++)
-    if (kQsaHandlerDataWordsG[h] > 0) c->qsa_data_words[hword(1, c->qsa_off[1][h]) & 0xFFFFu] = kQsaHandlerDataWordsG[h];
-  for (int q = 0; q < QK_COUNT; q++) {
-    const std::string n = kQsaKindNames[q];
-    c->qsa_vm_drain[q] = n == "PUSH_MEMB" || n.rfind("MEQK", 0) == 0 || n.rfind("UF1", 0) == 0;
-  }
+  const bool ok = c->qsa.build(off, base_lo);
   c->qsa_ready = ok && std::getenv("MQ_DISABLE_QSA") == nullptr;
   return MQ_OK;
 }
@@ -1191,12 +1151,12 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   // MQ_BMASK_CAP lowers the cap so tests reach the row path)
   std::vector<uint32_t> brows;
   {
-    c->bmask_of_var.assign(mb->n_vars, -1);
+    c->layout.bmask_of_var.assign(mb->n_vars, -1);
     size_t cap = 65535;
     if (const char* e = std::getenv("MQ_BMASK_CAP")) cap = std::min<size_t>(cap, (size_t)std::atol(e));
     for (int v = 0; v < mb->n_vars && brows.size() < cap; v++)
       if (mb->var_width[v] == 0) {
-        c->bmask_of_var[v] = (int32_t)brows.size();
+        c->layout.bmask_of_var[v] = (int32_t)brows.size();
         brows.push_back(voff[v]);
       }
     c->n_bmask = (int32_t)brows.size();
@@ -1205,10 +1165,10 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
     if (brows.empty()) brows.push_back(0);
     pk.add(c->bmask_rows, brows.data(), brows.size());
   }
-  c->var_off_h.assign(voff.begin(), voff.begin() + mb->n_vars);
-  c->var_nl_h.assign(vnl.begin(), vnl.begin() + mb->n_vars);
-  c->funcs_h.assign(mb->funcs, mb->funcs + F);
-  c->entry_words_n = F > 0 ? ew_total : 0;
+  c->layout.var_off.assign(voff.begin(), voff.begin() + mb->n_vars);
+  c->layout.var_nl.assign(vnl.begin(), vnl.begin() + mb->n_vars);
+  c->layout.funcs.assign(mb->funcs, mb->funcs + F);
+  c->layout.entry_words_n = F > 0 ? ew_total : 0;
   c->models_gen++;
   {
     std::vector<uint8_t> sig;
@@ -1219,10 +1179,10 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
     const int32_t nv = mb->n_vars;
     put(&nv, sizeof nv);
     put(mb->var_width, sizeof(uint16_t) * (size_t)nv);
-    put(c->bmask_of_var.data(), sizeof(int32_t) * c->bmask_of_var.size());
+    put(c->layout.bmask_of_var.data(), sizeof(int32_t) * c->layout.bmask_of_var.size());
     put(&F, sizeof F);
-    put(c->funcs_h.data(), sizeof(mq_func_desc) * c->funcs_h.size());
-    const uint8_t fits = (uint64_t)(c->entry_words_n + (int64_t)kEntryPadWords) * 4 < (1ull << 32) ? 1 : 0;
+    put(c->layout.funcs.data(), sizeof(mq_func_desc) * c->layout.funcs.size());
+    const uint8_t fits = (uint64_t)(c->layout.entry_words_n + (int64_t)kEntryPadWords) * 4 < (1ull << 32) ? 1 : 0;
     put(&fits, 1);
     if (sig != c->layout_sig) {
       c->layout_sig.swap(sig);
@@ -1364,7 +1324,7 @@ static int upload_one(mq_ctx* c, const mq_model_batch* mb, const mq_derivation* 
   c->index_base = mb->index_base;
   c->n_vars = mb->n_vars;
   c->n_funcs = F;
-  c->var_width.assign(mb->var_width, mb->var_width + mb->n_vars);
+  c->layout.var_width.assign(mb->var_width, mb->var_width + mb->n_vars);
   c->have_models = true;
   return MQ_OK;
 }
@@ -1676,7 +1636,7 @@ int mq_models_funcs_sizes(mq_ctx* c, int64_t sizes[4]) {
   if (!c || !c->peers.empty() || !sizes) return MQ_ERR_ARG;
   if (!c->have_models) return MQ_ERR_NO_MODELS;
   sizes[0] = (int64_t)c->n_funcs * (c->M + 1);
-  sizes[1] = c->n_funcs > 0 ? c->entry_words_n + (int64_t)kEntryPadWords : 0;
+  sizes[1] = c->n_funcs > 0 ? c->layout.entry_words_n + (int64_t)kEntryPadWords : 0;
   sizes[2] = c->else_words_n;
   sizes[3] = c->dense_words_n;
   return MQ_OK;
@@ -1720,7 +1680,7 @@ int mq_models_download_vars(mq_ctx* c, uint32_t* out, int64_t n_words) {
   if (!c || !c->peers.empty() || n_words < 0 || (n_words > 0 && !out)) return MQ_ERR_ARG;
   if (!c->have_models) return MQ_ERR_NO_MODELS;
   int64_t rows = 0;
-  for (uint32_t nl : c->var_nl_h) rows += nl;
+  for (uint32_t nl : c->layout.var_nl) rows += nl;
   if (n_words != rows * c->M) return MQ_ERR_ARG;
   if (n_words == 0) return MQ_OK;
   HIPCHK(hipSetDevice(c->device));
@@ -1773,737 +1733,6 @@ static unsigned long long* prof_buffer(mq_ctx* c, int level) {
   return c->prof.as<unsigned long long>();
 }
 
-// Count the handler kinds of one translated program (k = 0: P three-word entries; 1: G words,
-// inline constant words skipped) into hist[QK_COUNT] and, if given, kind bigrams into pairs.
-static void qsa_count(const mq_ctx* c, int k, const std::vector<uint32_t>& tr, std::vector<int64_t>& hist,
-                      std::vector<int64_t>* pairs) {
-  if (hist.size() != (size_t)QK_COUNT) hist.assign(QK_COUNT, 0);
-  if (pairs && pairs->size() != (size_t)QK_COUNT * QK_COUNT) pairs->assign((size_t)QK_COUNT * QK_COUNT, 0);
-  int prev = -1;
-  for (size_t i = 0; i < tr.size();) {
-    const uint32_t key = k == 0 ? ((tr[i] - c->qsa_hbase_lo[0]) >> 2) & 0xFFFFu : tr[i] & 0xFFFFu;
-    const int kind = c->qsa_kind_of[k].empty() ? -1 : c->qsa_kind_of[k][key];
-    i += k == 0 ? 3 : 1;
-    if (kind < 0) continue;
-    hist[kind]++;
-    if (pairs && prev >= 0 && kind != QK_REFILL) (*pairs)[(size_t)prev * QK_COUNT + kind]++;
-    if (kind != QK_REFILL) prev = kind;
-    if (k == 1) i += c->qsa_data_words[key];
-  }
-}
-
-// The program the assembly interpreter k runs: G's stack has kQsaStackG slots, so a deeper
-// program runs its spilled variant (tape_compiler.cpp CompiledTape::prog_g).
-static inline const std::vector<uint32_t>& qsa_prog(const CompiledTape& x, int k) {
-  return (k == 1 && !x.prog_g.empty()) ? x.prog_g : x.prog;
-}
-static inline int qsa_temps(const CompiledTape& x, int k) { return (k == 1 && !x.prog_g.empty()) ? x.n_temps_g : x.n_temps; }
-static inline int qsa_depth(const CompiledTape& x, int k) { return (k == 1 && !x.prog_g.empty()) ? x.depth_g : x.depth; }
-
-// Translate a compiled stack program into QSA threaded code for kernel k (0 = P, 1 = G).
-// models == false: structural check only (upload time: variable rows and function tables are
-// not known yet, any variable / lookup is assumed expressible).  extra: the tape's derived
-// constants (divisor reciprocals), appended after its own constants in the same order every
-// time.  Returns false if any instruction is outside the interpreter's set (those tapes run on
-// the HIP C++ kernel).  g_bail (the batch was uploaded under MQ_G_BAIL=1; verdict tapes only --
-// never column programs, mode 3): for G a bail point becomes its BAIL word where no PUSH_MEM load
-// can be outstanding, and the ops behind every bail point of the program follow the other
-// derived constants in `extra`.
-static bool qsa_translate(const mq_ctx* c, int k, bool models, const CompiledTape& x, std::vector<uint32_t>* out_p,
-                          std::vector<uint32_t>* extra_p, const std::vector<int>* gpre = nullptr,
-                          const std::vector<int>* gstage = nullptr, bool g_bail = false) {
-  std::vector<uint32_t> dummy_out, dummy_extra;
-  std::vector<uint32_t>& out = out_p ? *out_p : dummy_out;
-  std::vector<uint32_t>& extra = extra_p ? *extra_p : dummy_extra;
-  out.clear();
-  extra.clear();
-  const bool P = k == 0;
-  if (x.L != 8 || qsa_depth(x, k) > (P ? kQsaStackP : kQsaStackG) || qsa_temps(x, k) > kQsaMaxTemps) return false;
-  const std::vector<uint32_t>& xprog = qsa_prog(x, k);
-  const size_t wpi = P ? 3 : 1;   // program words per interpreter instruction
-  // every handler word emitted so far (position, key, immediate, inline data words): the
-  // fusions below rewrite the last ones while nothing follows them
-  struct Emit {
-    size_t pos;
-    int kind, d, v;
-    uint32_t imm;
-    size_t nd;
-  };
-  std::vector<Emit> log;
-  auto ends_at = [&](const Emit& e) { return e.pos + wpi + e.nd; };
-  auto drop_last = [&](size_t n) {   // forget the last n words (and their data)
-    out.resize(log[log.size() - n].pos);
-    log.resize(log.size() - n);
-  };
-  auto word = [&](int kind, int d, int v, uint32_t imm, bool imm32 = false) -> bool {
-    if (d < 0 || d >= kQsaStack || v < -1 || v >= kQsaSel || (imm > 0xFFFFu && !(imm32 && P))) return false;
-    const int h = c->qsa_index[k][kind][d][v + 1];
-    if (h < 0) return false;
-    log.push_back(Emit{out.size(), kind, d, v, imm, 0});
-    if (P) {   // entry: absolute handler address (low half), immediate, constant prefetch
-      out.push_back(c->qsa_hbase_lo[0] + c->qsa_off[0][h]);
-      out.push_back(imm);
-      out.push_back(0);
-    } else {
-      out.push_back(hword(k, c->qsa_off[k][h]) | (imm << 16));
-    }
-    return true;
-  };
-  // slot d holds a value of width W < 256: clear the bits above W
-  auto mask = [&](int d, uint32_t W) -> bool {
-    if (W >= 256) return true;
-    const int n = (int)(W + 31) / 32;
-    if (W % 32) return word(QK_MASKP, d, n - 1, W % 32);
-    return word(QK_MASKZ, d, n - 1, 0);
-  };
-  auto lshr = [&](int d, uint32_t kbits, bool arith) -> bool {
-    if (kbits == 0) return true;
-    return word(arith ? QK_ASHRI : QK_LSHRI, d, (int)(kbits >> 5), kbits & 31);
-  };
-  auto shl = [&](int d, uint32_t kbits) -> bool {
-    if (kbits == 0) return true;
-    if (kbits & 31) return word(QK_SHLI, d, (int)(kbits >> 5), 32 - (kbits & 31));
-    return word(QK_SHLW, d, (int)(kbits >> 5), 0);
-  };
-  // the constant pushed by the previous instruction (the right operand of a shift / division)
-  auto const_value = [&](uint32_t off, uint32_t (&v)[8]) -> bool {
-    if ((size_t)off + 8 > x.consts.size()) return false;
-    for (int l = 0; l < 8; l++) v[l] = x.consts[off + l];
-    return true;
-  };
-  // re-emit a word under another kind (same slot, selector, immediate and inline data)
-  auto rekind = [&](int kind) -> bool {
-    const Emit e = log.back();
-    if (c->qsa_index[k][kind][e.d][e.v + 1] < 0) return false;
-    std::vector<uint32_t> data(out.begin() + (long)(e.pos + wpi), out.begin() + (long)ends_at(e));
-    drop_last(1);
-    if (!word(kind, e.d, e.v, e.imm)) return false;
-    out.insert(out.end(), data.begin(), data.end());
-    log.back().nd = data.size();
-    return true;
-  };
-  // slot where the last word left a Bool result, or -1 (it is not a fusable Bool producer, or
-  // something was emitted after it)
-  auto last_bool_slot = [&]() -> int {
-    if (log.empty() || out.size() != ends_at(log.back()) || kQsaKindBoolRes[log.back().kind] < 0) return -1;
-    return kQsaKindBoolRes[log.back().kind] == 0 ? log.back().d : log.back().d - 1;
-  };
-  // AND / OR at slot d whose right operand the last word just produced: that word's fused form
-  auto fuse_acc = [&](int d, bool is_and) -> bool {
-    if (last_bool_slot() != d) return false;
-    const int fk = is_and ? kQsaKindAndForm[log.back().kind] : kQsaKindOrForm[log.back().kind];
-    return fk >= 0 && rekind(fk);
-  };
-  // NOT of a compare the last word just made: the complementary compare
-  auto fuse_not = [&](int d) -> bool {
-    if (last_bool_slot() != d || kQsaKindNot[log.back().kind] < 0) return false;
-    return rekind(kQsaKindNot[log.back().kind]);
-  };
-  // G: a constant push as the operand of a compare -> the compare-with-inline-constant handler.
-  // (cls, data words) of the constant pushed by e (PUSH_CONSTI / PUSH_CONSTW), or cls -1
-  auto const_of = [&](const Emit& e, std::vector<uint32_t>& words) -> int {
-    words.clear();
-    if (e.kind == QK_PUSH_CONSTI) return 0;
-    if (e.kind != QK_PUSH_CONSTW) return -1;
-    const size_t n = e.nd;
-    words.assign(out.begin() + (long)(e.pos + 1), out.begin() + (long)(e.pos + 1 + n));
-    const int cls = n <= (size_t)kQsaKClassWords[1] ? 1 : 2;
-    words.resize((size_t)kQsaKClassWords[cls], 0);
-    return cls;
-  };
-  auto emit_k = [&](int kind, int x, int sel, uint32_t imm, const std::vector<uint32_t>& words) -> bool {
-    if (!word(kind, x, sel, imm)) return false;
-    out.insert(out.end(), words.begin(), words.end());
-    log.back().nd = words.size();
-    return true;
-  };
-  // compare `kind` at slot d (operands S(d-1), S(d)); kk = its constant form, mk = the constant
-  // form of the mirrored compare (c OP x == x MIRROR(OP) c)
-  auto fuse_const = [&](int d, int kk, int mk) -> bool {
-    if (P || log.empty() || d < 1) return false;
-    std::vector<uint32_t> words;
-    const Emit e1 = log.back();
-    if (out.size() != ends_at(e1)) return false;
-    // constant on the right: S(d-1) OP c
-    if (e1.d == d) {
-      const int cls = const_of(e1, words);
-      if (cls >= 0 && c->qsa_index[k][kk][d - 1][cls + 1] >= 0) {
-        const uint32_t imm = e1.imm;
-        drop_last(1);
-        return emit_k(kk, d - 1, cls, cls == 0 ? imm : 0, words);
-      }
-    }
-    // constant on the left, value pushed right after it: the value moves down one slot
-    if (log.size() >= 2 && e1.d == d && e1.nd == 0 &&
-        (e1.kind == QK_PUSH_MEM || e1.kind == QK_PUSH_MEMS || e1.kind == QK_PUSH_TMP || e1.kind == QK_PUSH_VAR)) {
-      const Emit e0 = log[log.size() - 2];
-      const int cls = e0.d == d - 1 && ends_at(e0) == e1.pos ? const_of(e0, words) : -1;
-      if (cls >= 0 && c->qsa_index[k][mk][d - 1][cls + 1] >= 0 && c->qsa_index[k][e1.kind][d - 1][e1.v + 1] >= 0) {
-        const uint32_t imm = e0.imm;
-        drop_last(2);
-        return word(e1.kind, d - 1, e1.v, e1.imm) && emit_k(mk, d - 1, cls, cls == 0 ? imm : 0, words);
-      }
-    }
-    return false;
-  };
-  // G: consecutive "B(d - 1) &= packed mask" words (PUSH_PKB_A at slot d) as one PKBN_A word
-  // with up to four masks: their scalar loads share one wait
-  // ... and a PUSH_PKB at slot d - 1 followed by such words as one PKBP word at d - 1 (their AND
-  // pushed); up to six masks a word
-  auto merge_pkb = [&](int d) {
-    if (log.size() < 2) return;
-    const Emit e1 = log.back();
-    if (e1.kind != QK_PUSH_PKB_A || e1.d != d || out.size() != ends_at(e1)) return;
-    const Emit e0 = log[log.size() - 2];
-    if (ends_at(e0) != e1.pos) return;
-    int n0, kind, x;   // masks after the first one in e0; merged kind and slot
-    if (e0.d == d && e0.kind == QK_PUSH_PKB_A) n0 = 0, kind = QK_PKBN_A, x = d;
-    else if (e0.d == d && e0.kind == QK_PKBN_A) n0 = e0.v, kind = QK_PKBN_A, x = d;
-    else if (e0.d == d - 1 && e0.kind == QK_PUSH_PKB) n0 = 0, kind = QK_PKBP, x = d - 1;
-    else if (e0.d == d - 1 && e0.kind == QK_PKBP) n0 = e0.v, kind = QK_PKBP, x = d - 1;
-    else return;
-    if (n0 + 1 > 5 || c->qsa_index[k][kind][x][n0 + 2] < 0) return;
-    std::vector<uint32_t> data(out.begin() + (long)(e0.pos + 1), out.begin() + (long)ends_at(e0));
-    data.push_back(e1.imm);
-    const uint32_t imm0 = e0.imm;
-    drop_last(2);
-    emit_k(kind, x, n0 + 1, imm0, data);
-  };
-  // G: "PUSH_MEM / PUSH_MEMS x (n limbs); EQK_A x" (a model variable compared with an inline
-  // constant, AND-ed into the conjunction) as one M/SEQK{2,8}_A word: row / slot in the
-  // immediate, the constant in 2 or 8 inline data words (a 16-bit immediate constant travels
-  // as two)
-  // (and "PUSH_MEMS x; ULTK_A / UGTK_A x" as one S{ULT,UGT}K{2,8}_A word, same layout)
-  auto merge_memk = [&]() {
-    if (log.size() < 2) return;
-    const Emit e1 = log.back();
-    if ((e1.kind != QK_EQK_A && e1.kind != QK_ULTK_A && e1.kind != QK_UGTK_A) || out.size() != ends_at(e1)) return;
-    const Emit e0 = log[log.size() - 2];
-    if (ends_at(e0) != e1.pos || e0.d != e1.d || e0.nd != 0 || e0.v < 0) return;
-    const bool wide = e1.v == 2;
-    int fk;
-    if (e1.kind == QK_ULTK_A) {
-      if (e0.kind != QK_PUSH_MEMS) return;
-      fk = wide ? QK_SULTK8_A : QK_SULTK2_A;
-    } else if (e1.kind == QK_UGTK_A) {
-      if (e0.kind != QK_PUSH_MEMS) return;
-      fk = wide ? QK_SUGTK8_A : QK_SUGTK2_A;
-    } else if (e0.kind == QK_PUSH_MEM) fk = wide ? QK_MEQK8_A : QK_MEQK2_A;
-    else if (e0.kind == QK_PUSH_MEMS) fk = wide ? QK_SEQK8_A : QK_SEQK2_A;
-    else return;
-    if (c->qsa_index[k][fk][e1.d][e0.v + 1] < 0) return;
-    std::vector<uint32_t> data;
-    if (e1.v == 0) data = {e1.imm, 0u};
-    else data.assign(out.begin() + (long)(e1.pos + 1), out.begin() + (long)ends_at(e1));
-    const int x = e1.d, nsel = e0.v;
-    const uint32_t imm0 = e0.imm;
-    drop_last(2);
-    emit_k(fk, x, nsel, imm0, data);
-  };
-  // G: "PUSH_MEMS x (n limbs); SLTK / SGTK x" as one S{SLT,SGT}K{2,8} word (layout as merge_memk's)
-  auto merge_mems_k = [&]() {
-    if (P || log.size() < 2) return;
-    const Emit e1 = log.back();
-    if ((e1.kind != QK_SLTK && e1.kind != QK_SGTK) || out.size() != ends_at(e1)) return;
-    const Emit e0 = log[log.size() - 2];
-    if (e0.kind != QK_PUSH_MEMS || ends_at(e0) != e1.pos || e0.d != e1.d || e0.nd != 0 || e0.v < 0) return;
-    const bool wide = e1.v == 2;
-    const int fk = e1.kind == QK_SLTK ? (wide ? QK_SSLTK8 : QK_SSLTK2) : (wide ? QK_SSGTK8 : QK_SSGTK2);
-    if (c->qsa_index[k][fk][e1.d][e0.v + 1] < 0) return;
-    std::vector<uint32_t> data;
-    if (e1.v == 0) data = {e1.imm, 0u};
-    else data.assign(out.begin() + (long)(e1.pos + 1), out.begin() + (long)ends_at(e1));
-    const int x = e1.d, nsel = e0.v;
-    const uint32_t imm0 = e0.imm;
-    drop_last(2);
-    emit_k(fk, x, nsel, imm0, data);
-  };
-  // G: may a PUSH_MEM's vector loads be outstanding after the words emitted so far?  The final
-  // pass's rule, read backwards: a PUSH_MEM not yet followed by a stack reader (either wait form
-  // of one drains, or finds nothing to drain) or by a handler that waits for vector memory itself
-  auto push_mem_pending = [&]() -> bool {
-    for (size_t i = log.size(); i-- > 0;) {
-      if (log[i].kind == QK_PUSH_MEM) return true;
-      if (kQsaKindLForm[log[i].kind] >= 0 || c->qsa_vm_drain[log[i].kind]) return false;
-    }
-    return false;
-  };
-  // G under g_bail: the ops behind every bail point of the program, kept or dropped, in program
-  // order -- appended to `extra` after the division constants, whose offsets they leave alone (P
-  // translates the unspilled program, with its own bail points, against the same pool)
-  std::vector<uint32_t> bail_ops;
-  uint32_t prev_op = G_END, prev_d = 0, prev_imm = 0;
-  size_t prev_out = 0;
-  int prev_pre = -1;   // preload slot of the variable the previous instruction pushed
-  // preload slot of variable v in this kernel, or -1 (P: v itself; G: the batch's choice)
-  auto pre_slot = [&](uint32_t v) -> int {
-    if (P) return v < (uint32_t)kQsaVars ? (int)v : -1;
-    if (!models || !gpre || v >= gpre->size()) return -1;
-    return (*gpre)[v];
-  };
-  // a binary op at slot d whose right operand was just pushed from a preloaded variable runs
-  // as the fused handler kindv(d, slot) (the push word is dropped)
-  // (P) likewise a right operand just pushed from the constants, for the kinds with a kindc
-  // handler (operand read from SGPRs)
-  auto binop = [&](int d, int kind, int kindv, int kindc = -1, int kindk = -1, int kindkm = -1) -> bool {
-    // G: EQ of a constant (left) and a preloaded variable (right) -> EQVK, no stack traffic
-    if (!P && kind == QK_EQ && prev_op == G_PUSH_VAR && prev_pre >= 0 && (int)prev_d == d && log.size() >= 2 &&
-        out.size() == prev_out + wpi && log.back().pos == prev_out) {
-      const Emit e0 = log[log.size() - 2];
-      std::vector<uint32_t> words;
-      int cls = e0.d == d - 1 && ends_at(e0) == prev_out ? const_of(e0, words) : -1;
-      if (cls == 0) {   // the 16-bit immediate travels as a two-word constant here
-        words.assign((size_t)kQsaKClassWords[1], 0);
-        words[0] = e0.imm;
-        cls = 1;
-      }
-      const int sel = 2 * prev_pre + (cls - 1);
-      if (cls >= 1 && sel < kQsaSel && c->qsa_index[k][QK_EQVK][d - 1][sel + 1] >= 0) {
-        drop_last(2);
-        return emit_k(QK_EQVK, d - 1, sel, 0, words);
-      }
-    }
-    if (kindk >= 0 && fuse_const(d, kindk, kindkm)) return true;
-    if (prev_op == G_PUSH_VAR && prev_pre >= 0 && (int)prev_d == d && out.size() == prev_out + wpi &&
-        c->qsa_index[k][kindv][d][prev_pre + 1] >= 0) {
-      drop_last(1);
-      // (P) the left operand is a leaf pushed right before at slot d - 1: both leaves in one
-      // handler at d - 1 (gen_qsa.py kindVV / MULVV / kindCV, the right variable through M0)
-      int kvv = -1, kcv = -1;
-      bool vv_by_v1 = true;
-      switch (kindv) {
-        case QK_ADDV: kvv = QK_ADDVV; kcv = QK_ADDCV; break;
-        case QK_SUBV: kvv = QK_SUBVV; kcv = QK_SUBCV; break;
-        case QK_BANDV: kvv = QK_BANDVV; kcv = QK_BANDCV; break;
-        case QK_BORV: kvv = QK_BORVV; kcv = QK_BORCV; break;
-        case QK_BXORV: kvv = QK_BXORVV; kcv = QK_BXORCV; break;
-        case QK_MULV: kvv = QK_MULVV; kcv = QK_MULCV; vv_by_v1 = false; break;
-        default: break;
-      }
-      if (P && kvv >= 0 && d >= 1 && !log.empty() && out.size() == ends_at(log.back()) && log.back().d == d - 1) {
-        const Emit e0 = log.back();
-        const uint32_t v2 = 8u * (uint32_t)prev_pre;
-        if (e0.kind == QK_PUSH_VAR && e0.v >= 0 && c->qsa_index[k][kvv][d - 1][vv_by_v1 ? e0.v + 1 : 0] >= 0) {
-          drop_last(1);
-          return vv_by_v1 ? word(kvv, d - 1, e0.v, v2) : word(kvv, d - 1, -1, 8u * (uint32_t)e0.v | v2 << 16, true);
-        }
-        if (e0.kind == QK_PUSH_CONST && c->qsa_index[k][kcv][d - 1][0] >= 0) {
-          drop_last(1);
-          return word(kcv, d - 1, -1, e0.imm | v2 << 16, true);
-        }
-      }
-      return word(kindv, d, prev_pre, 0);
-    }
-    if (kindc >= 0 && P && prev_op == G_PUSH_CONST && (int)prev_d == d && out.size() == prev_out + wpi &&
-        c->qsa_index[k][kindc][d][0] >= 0) {
-      drop_last(1);
-      return word(kindc, d, -1, prev_imm);
-    }
-    return word(kind, d, -1, 0);
-  };
-  for (size_t pc = 0; pc < xprog.size(); pc++) {
-    const uint32_t w = xprog[pc];
-    const uint32_t op = w & 0xFFu, imm = w >> 12;
-    const int d = (int)((w >> 8) & 0xFu);
-    uint32_t imm2 = 0;
-    if (has_imm2(op)) {
-      if (++pc >= xprog.size()) return false;
-      imm2 = xprog[pc];
-    }
-    // a bail point is P's and, under MQ_G_BAIL=1 (g_bail), G's on verdict tapes.  G takes it
-    // only where no PUSH_MEM load can be outstanding (a load landing in a stack register after
-    // the next tape has started would corrupt that tape): at a spine point every push has been
-    // consumed by the compare that made B(0), which the emitted words must confirm.  Dropped, the
-    // word leaves the fusions' view of the previous instruction untouched.  (The ops behind it
-    // are recorded either way: every translation of a program lays its constants out the same.)
-    if (op == G_BAIL && !P) {
-      if (!g_bail) continue;
-      bail_ops.push_back(imm2);
-      if (d != 0 || bail_ops.size() > 0xFFFFu || push_mem_pending()) continue;
-    }
-    const size_t out_before = out.size();
-    const bool after_const = prev_op == G_PUSH_CONST && (int)prev_d == d;
-    int pushed_pre = -1;
-    bool ok;
-    switch (op) {
-      case G_END: ok = word(QK_END, 0, -1, 0); break;
-      // P: an entry without a constant (an ordinary non-PF_ entry to the constant prefetch
-      // pass); its 32-bit immediate is the ops the rest of the program would cost
-      // G: the ops do not fit the 16-bit immediate: it is the index into bail_ops here and
-      // becomes the word's offset in the tape's constants below (the handler loads it when it
-      // leaves the tape, and only then)
-      case G_BAIL: ok = d == 0 && (P ? word(QK_BAIL, 0, -1, imm2, true) : word(QK_BAIL, 0, -1, (uint32_t)bail_ops.size() - 1)); break;
-      case G_PUSH_VAR:
-      case G_PUSH_VAR_B: {
-        const bool b = op == G_PUSH_VAR_B;
-        const int ps = pre_slot(imm);
-        if (P) {
-          // preloaded variables only (var < 8, at most 256 bits)
-          ok = ps >= 0 && (!models || (imm < c->var_nl_h.size() && c->var_nl_h[imm] <= 8)) &&
-               word(b ? QK_PUSH_VARB : QK_PUSH_VAR, d, ps, 0);
-          pushed_pre = ps;
-        } else if (ps >= 0) {
-          ok = word(b ? QK_PUSH_VARB : QK_PUSH_VAR, d, ps, 0);
-          pushed_pre = ps;
-        } else if (!models) {
-          ok = word(b ? QK_PUSH_MEMB : QK_PUSH_MEM, d, b ? -1 : 7, 0);
-        } else if (b && imm < c->bmask_of_var.size() && c->bmask_of_var[imm] >= 0) {
-          // the tile's lane mask, one scalar load (qs_pack_bool)
-          ok = word(QK_PUSH_PKB, d, -1, (uint32_t)c->bmask_of_var[imm]);
-        } else if (gstage && imm < gstage->size() && (*gstage)[imm] >= 0 && c->var_nl_h[imm] <= 8) {
-          // a row staged in LDS by the workgroup (gen_qsa.py stage_rows)
-          ok = word(b ? QK_PUSH_MEMSB : QK_PUSH_MEMS, d, b ? -1 : (int)c->var_nl_h[imm] - 1, (uint32_t)(*gstage)[imm]);
-        } else {
-          ok = imm < c->var_off_h.size() && c->var_nl_h[imm] <= 8 && c->var_off_h[imm] <= 0xFFFFu &&
-               word(b ? QK_PUSH_MEMB : QK_PUSH_MEM, d, b ? -1 : (int)c->var_nl_h[imm] - 1, c->var_off_h[imm]);
-        }
-        break;
-      }
-      case G_PUSH_CONST: {
-        if (P) {
-          ok = word(QK_PUSH_CONST, d, -1, imm);
-          break;
-        }
-        // G: the constant travels inline in the program stream (no scalar load)
-        uint32_t cv[8];
-        ok = const_value(imm, cv);
-        if (!ok) break;
-        int n = 8;
-        while (n > 1 && cv[n - 1] == 0) n--;
-        if (n == 1 && cv[0] <= 0xFFFFu) {
-          ok = word(QK_PUSH_CONSTI, d, -1, cv[0]);
-        } else {
-          ok = word(QK_PUSH_CONSTW, d, n - 1, 0);
-          for (int l = 0; ok && l < n; l++) out.push_back(cv[l]);
-          if (ok) log.back().nd = (size_t)n;
-        }
-        break;
-      }
-      case G_PUSH_TMP: ok = word(QK_PUSH_TMP, d, -1, imm); break;
-      case G_PUSH_TMP_B: ok = word(QK_PUSH_TMP_BOOL, d, -1, imm); break;
-      case G_STORE_TMP: ok = d == 0 && word(QK_STORE_TMP, 0, -1, imm); break;
-      case G_STORE_TMP_B: ok = d == 0 && word(QK_STORE_TMP_BOOL, 0, -1, imm); break;
-      case G_PUSH_BOOL: ok = word(QK_PUSH_BOOL, d, -1, imm); break;
-      case G_NOT: ok = fuse_not(d) || word(QK_NOT, d, -1, 0); break;
-      case G_AND:
-        ok = fuse_acc(d, true) || word(QK_AND, d, -1, 0);
-        if (ok && !P) merge_pkb(d);
-        if (ok && !P) merge_memk();
-        break;
-      case G_OR: ok = fuse_acc(d, false) || word(QK_OR, d, -1, 0); break;
-      case G_XOR: ok = word(QK_XOR, d, -1, 0); break;
-      case G_IFF: ok = word(QK_IFF, d, -1, 0); break;
-      case G_IMPLIES: ok = word(QK_IMPLIES, d, -1, 0); break;
-      case G_BITE: ok = word(QK_BITE, d, -1, 0); break;
-      case G_BITE_EF: ok = word(QK_BITE_EF, d, -1, 0); break;
-      // unsigned predicates / bitwise / ite are exact on canonical values of any width <= 256
-      case G_EQ: ok = imm >= 1 && binop(d, QK_EQ, QK_EQV, QK_EQC, QK_EQK, QK_EQK); break;
-      case G_ULT: ok = imm >= 1 && binop(d, QK_ULT, QK_ULTV, QK_ULTC, QK_ULTK, QK_UGTK); break;
-      case G_ULE: ok = imm >= 1 && binop(d, QK_ULE, QK_ULEV, QK_ULEC, QK_ULEK, QK_UGEK); break;
-      case G_UGT: ok = imm >= 1 && binop(d, QK_UGT, QK_UGTV, QK_UGTC, QK_UGTK, QK_ULTK); break;
-      case G_UGE: ok = imm >= 1 && binop(d, QK_UGE, QK_UGEV, QK_UGEC, QK_UGEK, QK_ULEK); break;
-      case G_BAND: ok = binop(d, QK_BAND, QK_BANDV, QK_BANDC); break;
-      case G_BOR: ok = binop(d, QK_BOR, QK_BORV, QK_BORC); break;
-      case G_BXOR: ok = binop(d, QK_BXOR, QK_BXORV, QK_BXORC); break;
-      case G_ITE: {
-        // G: ite(c, x, 0) with the zero pushed last -> ITEZ at the then-slot (the push dropped)
-        const Emit* e = log.empty() ? nullptr : &log.back();
-        if (!P && d >= 2 && e && e->kind == QK_PUSH_CONSTI && e->imm == 0 && e->d == d && out.size() == ends_at(*e) &&
-            c->qsa_index[k][QK_ITEZ][d - 1][0] >= 0) {
-          drop_last(1);
-          // "SS{LT,GT}K x; PUSH_MEM x + 1": the load goes first, so it is in flight while the
-          // compare reads LDS (the compare touches slot x, T and B(x) only)
-          if (log.size() >= 2) {
-            const Emit ep = log.back(), ec = log[log.size() - 2];
-            const bool cmp = ec.kind == QK_SSLTK2 || ec.kind == QK_SSGTK2 || ec.kind == QK_SSLTK8 || ec.kind == QK_SSGTK8;
-            if (cmp && ep.kind == QK_PUSH_MEM && ep.nd == 0 && ep.d == d - 1 && ec.d == d - 2 &&
-                ends_at(ec) == ep.pos && out.size() == ends_at(ep)) {
-              std::vector<uint32_t> data(out.begin() + (long)(ec.pos + 1), out.begin() + (long)ends_at(ec));
-              drop_last(2);
-              ok = word(ep.kind, ep.d, ep.v, ep.imm) && emit_k(ec.kind, ec.d, ec.v, ec.imm, data);
-              if (!ok) break;
-            }
-          }
-          // a staged then-value pushed right before: ITEZS reads the row itself
-          const Emit ev = log.empty() ? Emit{} : log.back();
-          if (!log.empty() && ev.kind == QK_PUSH_MEMS && ev.nd == 0 && ev.d == d - 1 && ev.v >= 0 && out.size() == ends_at(ev) &&
-              c->qsa_index[k][QK_ITEZS][d - 1][ev.v + 1] >= 0) {
-            const int nsel = ev.v;
-            const uint32_t row = ev.imm;
-            drop_last(1);
-            ok = word(QK_ITEZS, d - 1, nsel, row);
-            break;
-          }
-          ok = word(QK_ITEZ, d - 1, -1, 0);
-        } else ok = word(QK_ITE, d, -1, 0);
-        break;
-      }
-      case G_ITE_EF: ok = word(QK_ITE_EF, d, -1, 0); break;
-      // signed predicates: at 256 bits the handler flips bit 255; below, flip bit W-1 of both
-      // operands (FLIP2) and compare unsigned
-      case G_SLT: case G_SLE: case G_SGT: case G_SGE: {
-        const int su = op == G_SLT ? QK_SLT : op == G_SLE ? QK_SLE : op == G_SGT ? QK_SGT : QK_SGE;
-        const int uu = op == G_SLT ? QK_ULT : op == G_SLE ? QK_ULE : op == G_SGT ? QK_UGT : QK_UGE;
-        if (imm == 256 && (op == G_SLT || op == G_SGT) &&
-            fuse_const(d, op == G_SLT ? QK_SLTK : QK_SGTK, op == G_SLT ? QK_SGTK : QK_SLTK)) {
-          // G: a compare with a constant operand; a staged variable pushed right before it is
-          // read by the compare itself (S{SLT,SGT}K{2,8})
-          merge_mems_k();
-          ok = true;
-        } else if (imm == 256) ok = word(su, d, -1, 0);
-        else ok = imm >= 1 && imm < 256 && word(QK_FLIP2, d, (int)((imm - 1) >> 5), (imm - 1) & 31) && word(uu, d, -1, 0);
-        break;
-      }
-      // wrapping arithmetic: 256-bit handlers, results below 256 bits re-masked
-      case G_ADD: ok = imm <= 256 && binop(d, QK_ADD, QK_ADDV, QK_ADDC) && mask(d - 1, imm); break;
-      case G_SUB: ok = imm <= 256 && binop(d, QK_SUB, QK_SUBV, QK_SUBC) && mask(d - 1, imm); break;
-      case G_MUL: ok = imm <= 256 && binop(d, QK_MUL, QK_MULV, QK_MULC) && mask(d - 1, imm); break;
-      case G_NEG: ok = imm <= 256 && word(QK_NEG, d, -1, 0) && mask(d, imm); break;
-      case G_BNOT: ok = imm <= 256 && word(QK_BNOT, d, -1, 0) && mask(d, imm); break;
-      // shifts by a constant amount (the previous instruction pushed it): in place on slot d-1
-      case G_SHL: case G_LSHR: case G_ASHR: {
-        uint32_t cv[8];
-        if (!after_const) {   // by a variable amount: G's SHLV / LSHRV / ASHRV (ASHR at 256 bits);
-          // the immediate is the width W: the handler replaces results of amounts >= W by the fill
-          ok = d >= 1 && imm >= 1 && imm <= 256 && (op != G_ASHR || imm == 256) &&
-               word(op == G_SHL ? QK_SHLV : op == G_LSHR ? QK_LSHRV : QK_ASHRV, d - 1, -1, imm) &&
-               (op != G_SHL || mask(d - 1, imm));
-          break;
-        }
-        ok = after_const && d >= 1 && imm >= 1 && imm <= 256 && const_value(prev_imm, cv);
-        if (!ok) break;
-        if (log.empty() || log.back().pos != prev_out) return false;
-        drop_last(1);  // drop the amount push
-        bool big = false;
-        for (int l = 1; l < 8; l++) big = big || cv[l] != 0;
-        const uint32_t kb = big || cv[0] >= imm ? imm : cv[0];  // >= width: everything shifted out
-        if (op == G_ASHR) {
-          ok = imm == 256 && lshr(d - 1, std::min<uint32_t>(kb, 255), true);
-        } else if (kb >= imm) {
-          ok = word(QK_MASKP, d - 1, 0, 0);  // zero
-        } else if (op == G_LSHR) {
-          ok = lshr(d - 1, kb, false);
-        } else {
-          ok = shl(d - 1, kb) && mask(d - 1, imm);
-        }
-        break;
-      }
-      // division by a constant divisor (the previous instruction pushed it), in place on d-1
-      case G_UDIV: case G_UREM: case G_SDIV: case G_SREM: case G_SMOD: {
-        uint32_t cv[8];
-        if (!after_const) {
-          // by a variable divisor: G's UDIVV / UREMV (both slots; the quotient of x / 0 is all
-          // ones, masked back to the width) and, at 256 bits, SDIVV / SREMV / SMODV
-          int kind = op == G_UDIV ? QK_UDIVV : op == G_UREM ? QK_UREMV : op == G_SDIV ? QK_SDIVV
-                   : op == G_SREM ? QK_SREMV : QK_SMODV;
-          const bool sgn = op == G_SDIV || op == G_SREM || op == G_SMOD;
-          ok = d >= 1 && imm >= 1 && imm <= 256 && (!sgn || imm == 256) && word(kind, d - 1, -1, 0) &&
-               (op != G_UDIV || mask(d - 1, imm));
-          break;
-        }
-        if (op == G_UDIV || op == G_UREM) {
-          // unsigned by a constant that is not a non-zero 32-bit value: UDIVV / UREMV on it
-          bool small = const_value(prev_imm, cv) && cv[0] != 0;
-          for (int l = 1; small && l < 8; l++) small = cv[l] == 0;
-          if (!small) {
-            ok = d >= 1 && imm >= 1 && imm <= 256 && word(op == G_UDIV ? QK_UDIVV : QK_UREMV, d - 1, -1, 0) &&
-                 (op == G_UREM || mask(d - 1, imm));
-            break;
-          }
-        }
-        ok = after_const && d >= 1 && imm >= 1 && imm <= 256 && const_value(prev_imm, cv);
-        if (!ok) break;
-        const bool sgn = op == G_SDIV || op == G_SREM || op == G_SMOD;
-        bool neg = false;
-        if (sgn) {
-          if (imm != 256) { ok = false; break; }
-          neg = (cv[7] >> 31) != 0;
-          if (neg) {  // |c| = -c
-            uint64_t br = 1;
-            for (int l = 0; l < 8; l++) {
-              const uint64_t t = (uint64_t)(uint32_t)~cv[l] + br;
-              cv[l] = (uint32_t)t;
-              br = t >> 32;
-            }
-          }
-        }
-        bool hi = false;
-        for (int l = 1; l < 8; l++) hi = hi || cv[l] != 0;
-        if (sgn && (hi || cv[0] == 0)) {
-          // a signed divisor of 0 or of magnitude >= 2^32: SDIVV / SREMV / SMODV on the pushed
-          // constant, as the unsigned case routes such divisors to UDIVV / UREMV (G only)
-          ok = word(op == G_SDIV ? QK_SDIVV : op == G_SREM ? QK_SREMV : QK_SMODV, d - 1, -1, 0);
-          break;
-        }
-        if (log.empty() || log.back().pos != prev_out) return false;
-        drop_last(1);  // drop the divisor push
-        if (!sgn && !hi && cv[0] != 0 && (cv[0] & (cv[0] - 1)) == 0) {
-          // unsigned power of two: shift / mask
-          const uint32_t kb = (uint32_t)__builtin_ctz(cv[0]);
-          ok = op == G_UDIV ? lshr(d - 1, kb, false)
-                            : (kb == 0 ? word(QK_MASKP, d - 1, 0, 0) : mask(d - 1, kb));
-          break;
-        }
-        if (hi || cv[0] == 0) { ok = false; break; }
-        const uint32_t cabs = cv[0];
-        const uint32_t sh = (uint32_t)__builtin_clz(cabs);
-        const uint32_t dn = cabs << sh;
-        const uint64_t inv = ~0ull / dn - (1ull << 32);
-        const uint32_t off = (uint32_t)(x.consts.size() + extra.size());
-        extra.push_back(dn);
-        extra.push_back((uint32_t)inv);
-        extra.push_back(sh);
-        extra.push_back(cabs);
-        int kind;
-        switch (op) {
-          case G_UDIV: kind = QK_UDIVC; break;
-          case G_UREM: kind = QK_UREMC; break;
-          case G_SREM: kind = QK_SREMC; break;
-          case G_SMOD: kind = neg ? QK_SMODCN : QK_SMODCP; break;
-          default: kind = neg ? QK_SDIVCN : QK_SDIVCP; break;
-        }
-        ok = word(kind, d - 1, -1, off);
-        break;
-      }
-      case G_EXTRACT:  // imm = lo, imm2 = result width
-        ok = imm < 256 && imm2 >= 1 && imm2 <= 256 && lshr(d, imm, false) && mask(d, imm2);
-        break;
-      case G_CONCAT:  // imm = width of the low operand (slot d), imm2 = result width
-        ok = imm >= 1 && imm < 256 && imm2 <= 256;
-        if (ok && !P && (imm & 31) && c->qsa_index[k][QK_SHLOR][d][(imm >> 5) + 1] >= 0)
-          ok = word(QK_SHLOR, d, (int)(imm >> 5), 32 - (imm & 31));   // G: shift and OR in one
-        else ok = ok && shl(d - 1, imm) && word(QK_BOR, d, -1, 0);
-        break;
-      case G_SEXT: {  // imm = source width, imm2 = result width
-        ok = imm >= 1 && imm <= 256 && imm2 <= 256;
-        if (!ok) break;
-        const int p = (int)((imm - 1) >> 5);
-        const uint32_t nb = ((imm - 1) & 31) + 1;
-        if (nb < 32) ok = word(QK_SEXTB, d, p, nb);
-        else if (p < 7) ok = word(QK_SEXTA, d, p, 0);
-        ok = ok && mask(d, imm2);
-        break;
-      }
-      case G_UF1: {  // imm = function id, imm2 = result width (0 = Bool)
-        // (G scans the entries with 32-bit byte offsets)
-        ok = !P && imm2 <= 256 && (uint64_t)(c->entry_words_n + (int64_t)kEntryPadWords) * 4 < (1ull << 32);
-        if (ok && models) {
-          // a function absent from the model batch evaluates to 0 (as in the C++ kernel)
-          ok = imm >= c->funcs_h.size() || (c->funcs_h[imm].arity == 1 && c->funcs_h[imm].arg_width[0] <= 256 &&
-                                            c->funcs_h[imm].result_width <= 256);
-        }
-        if (!ok) break;
-        if (imm2 == 0) ok = word(QK_UF1B, d, -1, imm);
-        else ok = word(QK_UF1, d, -1, imm) && mask(d, imm2);
-        break;
-      }
-      default: ok = false;
-    }
-    if (!ok) {
-      // MQ_QSA_DEBUG=1: name the stack-program instruction a translation stops at (diagnostic)
-      static const bool dbg = std::getenv("MQ_QSA_DEBUG") != nullptr;
-      if (dbg) std::fprintf(stderr, "qsa_translate(%s): op %u at slot %d imm %u not translated\n", P ? "P" : "G", op, d, imm);
-      return false;
-    }
-    prev_op = op;
-    prev_d = (uint32_t)d;
-    prev_imm = imm;
-    prev_out = out_before;
-    prev_pre = op == G_PUSH_VAR ? pushed_pre : -1;
-  }
-  static const bool no_lwait = std::getenv("MQ_NO_LWAIT") != nullptr;   // (diagnostic A/B)
-  if (!P) {
-    // final pass: a stack reader waits for the vector loads of a PUSH_MEM only when one may be
-    // outstanding; otherwise its "_L" variant waits for LDS / scalar loads alone, and the
-    // prefetch of the next program window (gen_qsa.py load_window) stays in flight
-    // (MQ_NO_LWAIT: no _L variants; END_V is needed either way)
-    bool pending = false;
-    std::vector<const Emit*> unsafe_bails;
-    for (const Emit& e : log) {
-      if (e.kind == QK_PUSH_MEM) {
-        pending = true;
-        continue;
-      }
-      if (e.kind == QK_BAIL) {
-        // this pass is the authority on loads in flight: a bail word it finds behind an
-        // outstanding PUSH_MEM goes (push_mem_pending kept it out when it was emitted)
-        if (pending) unsafe_bails.push_back(&e);
-        continue;
-      }
-      if (e.kind == QK_END) {
-        // the value a column stores may still be a load in flight: END_V waits for it (the
-        // tape end's column store waits for LDS / scalar loads only)
-        const int h = c->qsa_index[k][QK_END_V][0][0];
-        if (pending && h >= 0) out[e.pos] = hword(k, c->qsa_off[k][h]);
-        continue;
-      }
-      const int lk = kQsaKindLForm[e.kind];
-      if (lk >= 0) {
-        const int h = c->qsa_index[k][lk][e.d][e.v + 1];
-        if (!pending && h >= 0 && !no_lwait) out[e.pos] = hword(k, c->qsa_off[k][h]) | (e.imm << 16);
-        pending = false;   // (the VMWAIT form drained every load)
-        continue;
-      }
-      if (c->qsa_vm_drain[e.kind]) pending = false;
-    }
-    // the kept bail words name their ops by offset in the tape's constants; one past the
-    // immediate's reach goes too
-    const size_t bail_base = x.consts.size() + extra.size();
-    for (const Emit& e : log) {
-      if (e.kind != QK_BAIL) continue;
-      const size_t off = bail_base + e.imm;
-      const bool gone = std::find(unsafe_bails.begin(), unsafe_bails.end(), &e) != unsafe_bails.end();
-      if (off > 0xFFFFu && !gone) unsafe_bails.push_back(&e);
-      else if (!gone) out[e.pos] = (out[e.pos] & 0xFFFFu) | ((uint32_t)off << 16);
-    }
-    extra.insert(extra.end(), bail_ops.begin(), bail_ops.end());
-    std::sort(unsafe_bails.begin(), unsafe_bails.end());   // (log order = position order)
-    for (size_t i = unsafe_bails.size(); i-- > 0;)   // (last first: earlier positions stay valid)
-      out.erase(out.begin() + (long)unsafe_bails[i]->pos, out.begin() + (long)ends_at(*unsafe_bails[i]));
-  }
-  if (P) {
-    // constant prefetch (gen_qsa.py NEXT_P): a constant handler whose predecessor is not itself
-    // a prefetched one becomes its PF_ variant, and the predecessor's entry names its constant
-    // (the dispatch of the predecessor loads it into CB); a PF_ handler whose successor is not
-    // one re-loads its own constant (an in-flight load then writes CB's current contents)
-    auto pf_kind = [](int kind) -> int {
-      switch (kind) {
-        case QK_PUSH_CONST: return QK_PF_PUSH_CONST;
-        case QK_ADDC: return QK_PF_ADDC;
-        case QK_SUBC: return QK_PF_SUBC;
-        case QK_MULC: return QK_PF_MULC;
-        case QK_BANDC: return QK_PF_BANDC;
-        case QK_BORC: return QK_PF_BORC;
-        case QK_BXORC: return QK_PF_BXORC;
-        case QK_ADDCV: return QK_PF_ADDCV;
-        case QK_SUBCV: return QK_PF_SUBCV;
-        case QK_MULCV: return QK_PF_MULCV;
-        case QK_BANDCV: return QK_PF_BANDCV;
-        case QK_BORCV: return QK_PF_BORCV;
-        case QK_BXORCV: return QK_PF_BXORCV;
-        default: return -1;
-      }
-    };
-    std::vector<char> pf(log.size(), 0);
-    auto coff_bytes = [&](const Emit& e) -> uint32_t {
-      const bool cv = e.kind == QK_ADDCV || e.kind == QK_SUBCV || e.kind == QK_MULCV || e.kind == QK_BANDCV ||
-                      e.kind == QK_BORCV || e.kind == QK_BXORCV;
-      return 4u * (cv ? (e.imm & 0xFFFFu) : e.imm);
-    };
-    for (size_t j = 1; j < log.size(); j++) {
-      const Emit& e = log[j];
-      const int fk = pf_kind(e.kind);
-      if (fk < 0 || pf[j - 1] || c->qsa_index[0][fk][e.d][e.v + 1] < 0) continue;
-      pf[j] = 1;
-      out[e.pos] = c->qsa_hbase_lo[0] + c->qsa_off[0][c->qsa_index[0][fk][e.d][e.v + 1]];
-      out[log[j - 1].pos + 2] = coff_bytes(e);
-    }
-    for (size_t j = 0; j < log.size(); j++)
-      if (pf[j] && !(j + 1 < log.size() && pf[j + 1])) out[log[j].pos + 2] = coff_bytes(log[j]);
-  }
-  return x.consts.size() + extra.size() <= 0x10000u;
-}
-
 // Upload a compiled batch to ONE device.  may_move: the batch's last device takes the QSA-eligible
 // tapes' programs out of ct instead of copying them (~3 000 tapes of a fresh drop-in batch).
 static int tapes_upload_one(mq_ctx* c, int32_t n_tapes, std::vector<CompiledTape>& ct, mq_tapes** out,
@@ -2550,7 +1779,7 @@ static int tapes_upload_one(mq_ctx* c, int32_t n_tapes, std::vector<CompiledTape
     parallel_for(n_tapes, 32, [&](int, int64_t b, int64_t e) {
       for (int64_t t = b; t < e; t++)
         if (ct[t].supported && ct[t].L == 8 && ct[t].n_temps <= kQsaMaxTemps)
-          qsa_ok[t] = qsa_translate(c, 1, false, ct[t], nullptr, &qextra[t], nullptr, nullptr, T->g_bail) ? 1 : 0;
+          qsa_ok[t] = qsa_translate(c->qsa, c->layout, 1, false, ct[t], nullptr, &qextra[t], nullptr, nullptr, T->g_bail) ? 1 : 0;
     });
   pt.reset(new PhaseTimer(&c->host_t[2]));
   // (before the descriptor passes: with may_move they empty the eligible tapes' vectors)
@@ -3257,7 +2486,7 @@ static int set_columns_one(mq_tapes* T, const mq_tape_batch* progs, const int32_
   if (c->qsa_ready)
     for (int k = 0; k < n_columns; k++)
       gq[k] = !kcm[k] && !kpm[k] && ct[k].L == 8 && !ct[k].keccak && ct[k].n_temps <= kQsaMaxTemps &&
-              (int64_t)ct[k].n_nodes >= min_nodes && qsa_translate(c, 1, false, ct[k], nullptr, nullptr);
+              (int64_t)ct[k].n_nodes >= min_nodes && qsa_translate(c->qsa, c->layout, 1, false, ct[k], nullptr, nullptr);
   T->cq_ct.clear();
   T->cq_var.clear();
   T->cq_bool.clear();
@@ -3369,756 +2598,12 @@ static KArgs make_col_args(mq_ctx* c, mq_tapes* T, const mq_tapes::Variant& v) {
   return a;
 }
 
-// G programs stream through a 64-word VGPR window (gen_qsa.py NEXT_G): insert a REFILL word
-// wherever the next handler word and its inline data would not fit in the current window (the
-// refilled window starts right after the REFILL word).
-static void qsa_window_layout(const mq_ctx* c, std::vector<uint32_t>& prog) {
-  // Windows are the program's aligned 64-word blocks: a handler group (word + inline data) that
-  // does not fit the rest of a block is preceded by REFILL and moves to the next block (the gap
-  // is padded with END), and the program is padded to a whole block.  So the window after the
-  // current one is always 256 bytes further, which the kernel prefetches (gen_qsa.py NWIN), and
-  // the programs of consecutive descriptors are contiguous blocks: the next tape's first window
-  // is the prefetch of the current tape's last one.
-  const std::vector<uint8_t>& data_words = c->qsa_data_words;
-  const uint32_t refill = hword(1, c->qsa_off[1][c->qsa_index[1][QK_REFILL][0][0]]);
-  const uint32_t endw = hword(1, c->qsa_off[1][c->qsa_index[1][QK_END][0][0]]);
-  std::vector<uint32_t> out;
-  out.reserve(prog.size() + prog.size() / 32 + 64);
-  size_t pos = 0;
-  for (size_t i = 0; i < prog.size();) {
-    const size_t g = 1 + (size_t)data_words[prog[i] & 0xFFFFu];
-    if (pos + g > 63) {
-      out.push_back(refill);
-      out.insert(out.end(), 63 - pos, endw);
-      pos = 0;
-    }
-    for (size_t j = 0; j < g && i + j < prog.size(); j++) out.push_back(prog[i + j]);
-    pos += g;
-    i += g;
-  }
-  if (pos) out.insert(out.end(), 64 - pos, endw);
-  prog.swap(out);
-}
-
-// Column programs are short (C3: ~6 nodes): padding each to whole 64-word blocks made every column
-// start with a window load, a memory round trip per column program (the G profile charged it to
-// FRAME3: ~20 % of C3's cycles).  They are packed back to back instead: a program starts at the
-// next word (or, when its first handler group would not fit the block, at the next block), the
-// REFILL rule of qsa_window_layout applies inside it, and the kernel starts a program that lies in
-// its current window without a load (gen_qsa.py load_window).  Returns the program's word offset;
-// pos = the next word's position in its block.
-static uint32_t qsa_pack_program(const mq_ctx* c, std::vector<uint32_t>& out, size_t& pos,
-                                 const std::vector<uint32_t>& prog) {
-  const std::vector<uint8_t>& data_words = c->qsa_data_words;
-  const uint32_t refill = hword(1, c->qsa_off[1][c->qsa_index[1][QK_REFILL][0][0]]);
-  const uint32_t endw = hword(1, c->qsa_off[1][c->qsa_index[1][QK_END][0][0]]);
-  if (!prog.empty() && pos + 1 + (size_t)data_words[prog[0] & 0xFFFFu] > 63) {
-    out.insert(out.end(), 64 - pos, endw);
-    pos = 0;
-  }
-  const uint32_t start = (uint32_t)out.size();
-  for (size_t i = 0; i < prog.size();) {
-    const size_t g = 1 + (size_t)data_words[prog[i] & 0xFFFFu];
-    if (pos + g > 63) {
-      out.push_back(refill);
-      out.insert(out.end(), 63 - pos, endw);
-      pos = 0;
-    }
-    for (size_t j = 0; j < g && i + j < prog.size(); j++) out.push_back(prog[i + j]);
-    pos += g;
-    i += g;
-  }
-  return start;
-}
-
-// Push counts of the variables (<= 256 bits) a set of compiled programs reads.
-static std::vector<int64_t> count_pushes(const mq_ctx* c, const std::vector<CompiledTape>& cts,
-                                         const std::vector<char>* skip = nullptr) {
-  std::vector<int64_t> pushes(c->var_nl_h.size(), 0);
-  for (size_t i = 0; i < cts.size(); i++) {
-    if (skip && (*skip)[i]) continue;
-    const auto& pr = cts[i].prog;
-    for (size_t pc = 0; pc < pr.size(); pc++) {
-      const uint32_t op = pr[pc] & 0xFFu, imm = pr[pc] >> 12;
-      if ((op == G_PUSH_VAR || (op == G_PUSH_VAR_B && !(imm < c->bmask_of_var.size() && c->bmask_of_var[imm] >= 0))) &&
-          imm < pushes.size() && c->var_nl_h[imm] <= 8)
-        pushes[imm]++;
-      if (has_imm2(op)) pc++;
-    }
-  }
-  return pushes;
-}
-
-// G kernel LDS staging plan: the most pushed variables (not preloaded) whose rows fit the
-// workgroup's staging budget get consecutive LDS slots (gen_qsa.py stage_rows); their pushes
-// become LDS reads.  Budget: MQ_G_STAGE_KB (default 26: the 80-VGPR G runs 6 waves per SIMD =
-// 6 workgroups of 4 waves per CU, and 6 x 26 KB fit the CU's 160 KB; 40 KB, the budget of the
-// 5-wave layout, capped C5 at 4 workgroups per CU: 70.5 vs 61.6 ms, profiles/r04c) KB per
-// workgroup minus the temps of its 4 waves.  Every workgroup loads its rows
-// once, so a variable is staged only when the workgroup's tapes (wg_share of the batch's
-// programs) push it at least MQ_G_STAGE_MIN (default 1.5) times on average
-// (profiles/r02t_*: 40 KB with no such floor sped C3 up and slowed C5, whose groups cover few
-// tapes).  stage_rows is padded to a multiple of 8 with the zero row.
 static int64_t g_tapes_per_group(int64_t n, int64_t M);
 static int64_t cq_tapes_per_group(int64_t n, int64_t M);
-
-
-static void plan_stage(const mq_ctx* c, const std::vector<int64_t>& pushes, const std::vector<int>* gpre, int temps,
-                       double wg_share, std::vector<int>& gstage, std::vector<uint32_t>& rows) {
-  int64_t kb = 26;
-  if (const char* e = std::getenv("MQ_G_STAGE_KB")) kb = std::atol(e);
-  double min_pushes = 1.5;
-  if (const char* e = std::getenv("MQ_G_STAGE_MIN")) min_pushes = std::atof(e);
-  const int64_t budget = (kb * 1024 - 4 * (int64_t)temps * 2048) / 256;
-  gstage.assign(c->var_nl_h.size(), -1);
-  rows.clear();
-  std::vector<int> order;
-  for (size_t v = 0; v < pushes.size(); v++)
-    if (pushes[v] > 0 && !(gpre && v < gpre->size() && (*gpre)[v] >= 0)) order.push_back((int)v);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pushes[a] > pushes[b]; });
-  for (int v : order) {
-    const int64_t nl = c->var_nl_h[v];
-    if ((double)pushes[v] * wg_share < min_pushes) break;   // (sorted by pushes)
-    if ((int64_t)rows.size() + nl > budget) continue;
-    gstage[v] = (int)rows.size();
-    for (int64_t l = 0; l < nl; l++) rows.push_back(c->var_off_h[v] + (uint32_t)l);
-  }
-  const uint32_t zero_row = (uint32_t)(c->var_off_h.empty() ? 0 : c->var_off_h.back() + c->var_nl_h.back());
-  while (rows.size() % 8) rows.push_back(zero_row);
-}
 
 // (Re)translate the QSA-eligible tapes for the current model batch (variable rows, function
 // table): the P kernel when every variable a tape reads is preloaded, the G kernel otherwise.
 // If one tape does not translate, the whole group runs on the HIP C++ kernel for this batch.
-// A flat conjunction (fc.hip): the stack program of x, run abstractly, leaves an AND of Bool
-// variables (negated or not) and compares of one model variable of at most 256 bits with a
-// constant; temps, arithmetic and anything else do not match.  A Bool variable without a lane-mask
-// index is a compare of its 0/1 row with 1.  Appends its masks (index | negated << 31) and
-// compares (FcCmpH: the variable's first row and limbs, the predicate as an accept mask over
-// (x < c, x == c, x > c), the constant; signed compares have the sign bit flipped) to the lists.
-struct FcCmpH {
-  uint32_t row, nl, accept;
-  uint32_t c[8], f[8];
-  uint32_t src_nl = 0;   // limbs of the compared variable's rows (0: nl; fewer when it was zero-extended)
-  uint32_t nx = 0;       // unary atoms (fca only): the variable's transform, nx steps
-  FcXop xf[kFcMaxXops] = {};
-};
-// accept masks: bit 0 x < c, bit 1 x == c, bit 2 x > c
-static constexpr uint32_t kAccEq = 2, kAccNe = 5, kAccLt = 1, kAccLe = 3, kAccGt = 4, kAccGe = 6;
-// LDS budget of the flat-conjunction kernel's staging, per tile (fc.hip stages FC_TILES = 4
-// tiles a workgroup): rows of 256 B (40 KB for 4 tiles) and masks of 8 B (8 KB for 4 tiles);
-// only what a launch uses is allocated (C4's tapes: ~5 KB)
-static constexpr int kFcStageRows = 40;
-static constexpr int kFcStageMasks = 256;
-
-// A program that is a flat conjunction of atoms (Bool variables, variable-constant compares),
-// or the negation of one: ORs of atoms and of negated conjunctions are taken by De Morgan
-// (OR(a, b) = NOT(AND(NOT a, NOT b))), the result negation returned in *neg.
-// With `unary` (the two-phase kernel only) an atom may also compare a constant with a unary
-// function of its variable: zero extension (free: values are canonical), sign extension, extract,
-// shifts by constants, and division / remainder by small constants (FcXop, fc.hip fx_apply).
-static bool fc_match(const mq_ctx* c, const CompiledTape& x, std::vector<uint32_t>& masks, std::vector<FcCmpH>& cmps,
-                     bool* neg = nullptr, bool unary = false) {
-  struct Item {
-    int kind = 0;   // 0 model variable (BV, through xf), 1 constant, 2 conjunction (negated when neg)
-    uint32_t v = 0;
-    uint32_t w = 0;   // kind 0: the width of its current value
-    bool neg = false;
-    std::vector<uint32_t> m;
-    std::vector<FcCmpH> q;
-    std::vector<FcXop> xf;
-  };
-  // the 256-bit constant at word offset k of the tape's pool, limb by limb (8 limbs, zero padded)
-  auto const_limbs = [&](uint32_t k, uint32_t out[8]) {
-    for (int i = 0; i < 8; i++) out[i] = x.consts[k + i];
-  };
-  // value (< 2^32 or saturated) of a constant of width w: its limbs above 0 are zero?
-  auto small_value = [&](const uint32_t l[8], uint64_t* v) {
-    for (int i = 2; i < 8; i++)
-      if (l[i]) return false;
-    *v = (uint64_t)l[0] | ((uint64_t)l[1] << 32);
-    return true;
-  };
-  // NOT of an item as a plain conjunction: a single atom negated, or a negated conjunction's body
-  auto negate_to_conj = [](Item& a) -> bool {
-    if (a.neg) {
-      a.neg = false;
-      return true;
-    }
-    if (a.m.size() + a.q.size() != 1) return false;
-    if (!a.m.empty()) a.m[0] ^= 0x80000000u;
-    else a.q[0].accept ^= 7u;
-    return true;
-  };
-  std::vector<Item> st;
-  const auto& pr = x.prog;
-  auto bool_item = [&](uint32_t v, Item& it) {
-    it.kind = 2;
-    if (v < c->bmask_of_var.size() && c->bmask_of_var[v] >= 0) {
-      it.m.push_back((uint32_t)c->bmask_of_var[v]);
-    } else {
-      FcCmpH q{};
-      q.row = c->var_off_h[v];
-      q.nl = 1;
-      q.accept = kAccEq;
-      q.c[0] = 1;
-      it.q.push_back(q);
-    }
-  };
-  for (size_t pc = 0; pc < pr.size(); pc++) {
-    const uint32_t w = pr[pc], op = w & 0xFFu, imm = w >> 12;
-    if (op == G_END) break;
-    if (unary && op == G_CONCAT && pc + 1 < pr.size()) {
-      // Concat(0, x): a zero extension (bitvec.py:16-22 pads a narrower operand so; EVM BYTE)
-      const uint32_t w2 = pr[++pc];
-      if (st.size() < 2 || st.back().kind != 0 || st[st.size() - 2].kind != 1 || st.back().w > imm || w2 > 256) return false;
-      uint32_t hl[8];
-      const_limbs(st[st.size() - 2].v, hl);
-      for (int i = 0; i < 8; i++)
-        if (hl[i]) return false;
-      Item v = std::move(st.back());
-      st.pop_back();
-      st.back() = std::move(v);
-      st.back().w = w2;
-      continue;
-    }
-    if (unary && (op == G_EXTRACT || op == G_SEXT) && pc + 1 < pr.size()) {
-      // (the two ops with a second word: the result width)
-      const uint32_t w2 = pr[++pc];
-      if (st.empty() || st.back().kind != 0 || st.back().xf.size() >= (size_t)kFcMaxXops) return false;
-      Item& a = st.back();
-      // (a value narrower than the op's operand was zero-extended: canonical values are, so the
-      // op reads it at the wider width as is)
-      if (op == G_EXTRACT) {
-        if (imm + w2 > 256 || w2 == 0) return false;
-        a.xf.push_back(FcXop{FX_EXTRACT | (std::max(a.w, imm + w2) << 8), imm, w2, 0});
-      } else {
-        if (imm < a.w || w2 <= imm || w2 > 256) return false;
-        a.xf.push_back(FcXop{FX_SEXT | (imm << 8), w2, 0, 0});
-      }
-      a.w = w2;
-      continue;
-    }
-    if (op == G_BAIL) {   // (a flat conjunction is too cheap to carry one; skipped all the same)
-      pc++;
-      continue;
-    }
-    if (has_imm2(op)) return false;
-    Item it;
-    switch (op) {
-      case G_PUSH_VAR:
-        if (imm >= c->var_nl_h.size() || c->var_width[imm] == 0 || c->var_nl_h[imm] > 8) return false;
-        it.kind = 0;
-        it.v = imm;
-        it.w = c->var_width[imm];
-        st.push_back(std::move(it));
-        break;
-      case G_LSHR: case G_SHL: case G_ASHR: case G_UREM: case G_UDIV: case G_SMOD: case G_SREM: case G_SDIV: {
-        // a unary step: the variable (through its steps so far) OP a constant
-        if (!unary || st.size() < 2 || st.back().kind != 1 || st[st.size() - 2].kind != 0) return false;
-        const uint32_t kc = st.back().v;
-        st.pop_back();
-        Item& a = st.back();
-        const uint32_t w = imm;   // (>= the value's width: a zero-extended value, read as is)
-        if (imm < a.w || w == 0 || w > 256 || a.xf.size() >= (size_t)kFcMaxXops) return false;
-        uint32_t l[8];
-        const_limbs(kc, l);
-        uint64_t k = 0;
-        const bool small = small_value(l, &k);
-        if (op == G_LSHR || op == G_SHL || op == G_ASHR) {
-          const uint32_t sh = (!small || k >= w) ? w : (uint32_t)k;   // (>= w: the kernel's saturation)
-          a.xf.push_back(FcXop{(op == G_LSHR ? FX_LSHR : op == G_SHL ? FX_SHL : FX_ASHR) | (w << 8), sh, 0, 0});
-        } else if (op == G_UREM || op == G_UDIV) {
-          if (!small || k == 0 || k >= (1u << 21)) return false;
-          a.xf.push_back(FcXop{(op == G_UREM ? FX_UREM : FX_UDIV) | (w << 8), (uint32_t)k, 0, 0});
-        } else {
-          // signed divisor: |d| and its sign at width w (two's complement of the w-bit constant)
-          bool dneg = ((l[(w - 1) / 32] >> ((w - 1) % 32)) & 1u) != 0;
-          uint32_t m[8];
-          for (int i = 0; i < 8; i++) m[i] = l[i];
-          if (dneg) {   // |d| = -d mod 2^w
-            uint64_t cy = 1;
-            for (int i = 0; i < 8; i++) {
-              const uint64_t t = (uint64_t)(~m[i]) + cy;
-              m[i] = (uint32_t)t;
-              cy = t >> 32;
-            }
-            for (int i = 0; i < 8; i++) {
-              const uint32_t lo = 32u * i;
-              if (w <= lo) m[i] = 0;
-              else if (w < lo + 32) m[i] &= (1u << (w - lo)) - 1u;
-            }
-          }
-          uint64_t ad = 0;
-          if (!small_value(m, &ad) || ad == 0 || ad >= (1u << 21)) return false;
-          const uint32_t code = op == G_SMOD ? FX_SMOD : op == G_SREM ? FX_SREM : FX_SDIV;
-          a.xf.push_back(FcXop{code | (w << 8), (uint32_t)ad, dneg ? 1u : 0u, 0});
-        }
-        a.w = w;
-        break;
-      }
-      case G_PUSH_VAR_B:
-        if (imm >= c->var_nl_h.size() || c->var_width[imm] != 0) return false;
-        bool_item(imm, it);
-        st.push_back(std::move(it));
-        break;
-      case G_PUSH_CONST:
-        if ((size_t)imm + 8 > x.consts.size()) return false;
-        it.kind = 1;
-        it.v = imm;
-        st.push_back(std::move(it));
-        break;
-      case G_PUSH_BOOL:
-        if (imm != 1) return false;
-        it.kind = 2;   // TRUE: the empty conjunction
-        st.push_back(std::move(it));
-        break;
-      case G_NOT: {
-        if (st.empty() || st.back().kind != 2) return false;
-        Item& a = st.back();
-        if (!negate_to_conj(a)) a.neg = true;   // NOT of a conjunction of several atoms
-        break;
-      }
-      case G_AND: case G_OR: {
-        if (st.size() < 2 || st.back().kind != 2 || st[st.size() - 2].kind != 2) return false;
-        Item b = std::move(st.back());
-        st.pop_back();
-        Item& a = st.back();
-        if (op == G_OR) {   // NOT(AND(NOT a, NOT b))
-          if (!negate_to_conj(a) || !negate_to_conj(b)) return false;
-          a.neg = true;
-        } else if (a.neg || b.neg) {
-          return false;
-        }
-        a.m.insert(a.m.end(), b.m.begin(), b.m.end());
-        a.q.insert(a.q.end(), b.q.begin(), b.q.end());
-        break;
-      }
-      case G_EQ: case G_ULT: case G_ULE: case G_UGT: case G_UGE:
-      case G_SLT: case G_SLE: case G_SGT: case G_SGE: {
-        if (st.size() < 2) return false;
-        Item r = std::move(st.back());
-        st.pop_back();
-        Item l = std::move(st.back());
-        st.pop_back();
-        bool swap;
-        if (l.kind == 0 && r.kind == 1) swap = false;
-        else if (l.kind == 1 && r.kind == 0) swap = true;
-        else if (unary && l.kind == 1 && r.kind == 1 && imm > 0 && imm <= 256 && !c->var_off_h.empty()) {
-          // two constants (an unfolded compare): its truth value — TRUE is the empty
-          // conjunction, FALSE an atom that accepts nothing
-          uint32_t a[8], b[8];
-          const_limbs(l.v, a);
-          const_limbs(r.v, b);
-          if (op >= G_SLT) {
-            a[(imm - 1) / 32] ^= 1u << ((imm - 1) % 32);
-            b[(imm - 1) / 32] ^= 1u << ((imm - 1) % 32);
-          }
-          int cmp = 0;
-          for (int i = 7; i >= 0 && !cmp; i--) cmp = a[i] < b[i] ? -1 : (a[i] > b[i] ? 1 : 0);
-          bool t;
-          switch (op) {
-            case G_EQ: t = cmp == 0; break;
-            case G_ULT: case G_SLT: t = cmp < 0; break;
-            case G_ULE: case G_SLE: t = cmp <= 0; break;
-            case G_UGT: case G_SGT: t = cmp > 0; break;
-            default: t = cmp >= 0; break;
-          }
-          it.kind = 2;
-          if (!t) {
-            FcCmpH q{};
-            q.row = c->var_off_h[0];
-            q.nl = 1;
-            q.accept = 0;
-            it.q.push_back(q);
-          }
-          st.push_back(std::move(it));
-          break;
-        } else {
-          return false;
-        }
-        const Item& var = swap ? r : l;
-        const Item& cst = swap ? l : r;
-        const uint32_t wdt = imm;
-        // (a narrower value compared at a wider width: a zero-extended column read, free)
-        if (wdt == 0 || wdt > 256 || var.w > wdt || (!unary && (var.w != wdt || !var.xf.empty()))) return false;
-        FcCmpH q{};
-        q.row = c->var_off_h[var.v];
-        q.nl = (wdt + 31) / 32;
-        q.src_nl = c->var_nl_h[var.v];
-        q.nx = (uint32_t)var.xf.size();
-        for (size_t k = 0; k < var.xf.size(); k++) q.xf[k] = var.xf[k];
-        for (uint32_t i = 0; i < q.nl; i++) q.c[i] = x.consts[cst.v + i];
-        // x OP c with the variable on the left; a constant on the left mirrors the order
-        switch (op) {
-          case G_EQ: q.accept = kAccEq; break;
-          case G_ULT: case G_SLT: q.accept = swap ? kAccGt : kAccLt; break;
-          case G_ULE: case G_SLE: q.accept = swap ? kAccGe : kAccLe; break;
-          case G_UGT: case G_SGT: q.accept = swap ? kAccLt : kAccGt; break;
-          default: q.accept = swap ? kAccLe : kAccGe; break;
-        }
-        if (op >= G_SLT) {   // signed: flip the sign bit of both sides, then compare unsigned
-          q.f[q.nl - 1] = 1u << ((wdt - 1) % 32);
-          q.c[q.nl - 1] ^= q.f[q.nl - 1];
-        }
-        it.kind = 2;
-        it.q.push_back(q);
-        st.push_back(std::move(it));
-        break;
-      }
-      default:
-        return false;
-    }
-  }
-  if (st.size() != 1 || st[0].kind != 2) return false;
-  if (st[0].neg && !neg) return false;
-  if (neg) *neg = st[0].neg;
-  masks.insert(masks.end(), st[0].m.begin(), st[0].m.end());
-  cmps.insert(cmps.end(), st[0].q.begin(), st[0].q.end());
-  return true;
-}
-
-// The flat-conjunction kernel's tables for the tapes (or columns) `cand` of the lists `fm` / `fq`
-// (fc_match): the compared variables and the masks the most compares / tapes read are staged in
-// LDS within the budgets; a candidate reading one that is not staged is dropped from `cand`'s
-// kernel (keep[i] = 0: it stays on the interpreter).  out_of(i) and mask_out(i) give FcTape.out /
-// .mask_out, nodes_ops(i) its metric words.
-struct FcPlan {
-  std::vector<FcTape> tapes;
-  std::vector<uint32_t> mask_lds;
-  std::vector<FcCmp> cmps;
-  std::vector<uint32_t> stage_rows, stage_masks;
-  std::vector<unsigned long long> prefix;
-};
-static void fc_plan(const mq_ctx* c, const std::vector<std::vector<uint32_t>>& fm, const std::vector<std::vector<FcCmpH>>& fq,
-                    const std::vector<char>& negated, std::vector<char>& keep, const std::function<uint32_t(size_t)>& out_of,
-                    const std::function<int32_t(size_t)>& mask_out,
-                    const std::function<std::pair<uint32_t, uint32_t>(size_t)>& nodes_ops, FcPlan& P) {
-  const uint32_t zero_row = (uint32_t)(c->var_off_h.empty() ? 0 : c->var_off_h.back() + c->var_nl_h.back());
-  std::map<uint32_t, int64_t> row_use, mask_use;
-  std::map<uint32_t, uint32_t> row_nl;
-  for (size_t i = 0; i < keep.size(); i++) {
-    if (!keep[i]) continue;
-    for (const auto& q : fq[i]) {
-      row_use[q.row]++;
-      row_nl[q.row] = q.nl;
-    }
-    for (uint32_t e : fm[i]) mask_use[e & 0x7FFFFFFFu]++;
-  }
-  auto by_use = [](const std::map<uint32_t, int64_t>& u) {
-    std::vector<std::pair<int64_t, uint32_t>> o;
-    for (const auto& kv : u) o.push_back({kv.second, kv.first});
-    std::stable_sort(o.begin(), o.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-    return o;
-  };
-  std::map<uint32_t, uint32_t> slot_of, mslot_of;
-  for (const auto& o : by_use(row_use)) {
-    const uint32_t nl = row_nl[o.second], width = nl <= 2 ? 2 : 8;   // (padded with the zero row)
-    if (P.stage_rows.size() + width > (size_t)kFcStageRows) continue;
-    slot_of[o.second] = (uint32_t)P.stage_rows.size();
-    for (uint32_t l = 0; l < width; l++) P.stage_rows.push_back(l < nl ? o.second + l : zero_row);
-  }
-  for (const auto& o : by_use(mask_use)) {
-    if (P.stage_masks.size() >= (size_t)kFcStageMasks) break;
-    mslot_of[o.second] = (uint32_t)P.stage_masks.size();
-    P.stage_masks.push_back(o.second);
-  }
-  P.prefix.assign(2, 0);
-  for (size_t i = 0; i < keep.size(); i++) {
-    if (!keep[i]) continue;
-    bool ok = true;
-    for (const auto& q : fq[i]) ok = ok && slot_of.count(q.row);
-    for (uint32_t e : fm[i]) ok = ok && mslot_of.count(e & 0x7FFFFFFFu);
-    if (!ok) {
-      keep[i] = 0;
-      continue;
-    }
-    FcTape f{};
-    f.out = out_of(i);
-    f.mask_out = mask_out(i);
-    f.mask_off = (uint32_t)P.mask_lds.size();
-    f.n_mask = (uint32_t)fm[i].size() | (negated[i] ? 0x80000000u : 0u);
-    for (uint32_t e : fm[i]) P.mask_lds.push_back(8u * mslot_of[e & 0x7FFFFFFFu] | (e >> 31));
-    if (!fm[i].empty())
-      while (P.mask_lds.size() % 16) P.mask_lds.push_back(P.mask_lds.back());   // (the same AND again)
-    f.cmp_off = (uint32_t)P.cmps.size();
-    f.n_cmp = (uint32_t)fq[i].size();
-    for (const auto& h : fq[i]) {
-      FcCmp q{};
-      q.h.slot = slot_of[h.row];
-      q.h.nl = h.nl;
-      q.h.accept = h.accept;
-      q.h.c01 = (uint64_t)h.c[0] | ((uint64_t)h.c[1] << 32);
-      q.h.f01 = (uint64_t)h.f[0] | ((uint64_t)h.f[1] << 32);
-      for (int l = 0; l < 6; l++) {
-        q.t.c[l] = h.c[2 + l];
-        q.t.f[l] = h.f[2 + l];
-      }
-      P.cmps.push_back(q);
-    }
-    const auto no = nodes_ops(i);
-    f.n_nodes = no.first;
-    f.alg_ops = no.second;
-    P.tapes.push_back(f);
-    P.prefix.push_back(P.prefix[P.prefix.size() - 2] + f.n_nodes);
-    P.prefix.push_back(P.prefix[P.prefix.size() - 2] + f.alg_ops);
-  }
-}
-
-// The two-phase kernel's tables for the tapes `keep` of fm / fq (fca_kernel).  Tapes are taken
-// in order into launches ("segments") of at most kFcaMaxAtoms distinct compares ("atoms": a
-// compare and its negation are one atom, accept canonicalised to {1, 2, 3} and the negation moved
-// into the list entry) and kFcStageMasks distinct Bool masks; a segment's atoms are ordered by
-// the variable they read (one group per variable: its limbs are loaded once per tile).
-struct FcaPlan {
-  std::vector<FcCmp> atoms;
-  std::vector<FcXf> xfs;   // parallel to atoms
-  bool any_xf = false;     // some atom has a unary transform (else the launches pass xfs = nullptr)
-  std::vector<FcaGroup> groups;
-  std::vector<uint32_t> lists, chunk_off, tape_out, metric, stage_masks;
-  std::vector<int32_t> col_mask;   // (columns: per kept column its lane-mask index)
-  std::vector<FcaPlanSeg> segs;
-};
-static constexpr int kFcaMaxAtoms = 1024;   // 32 KB of LDS masks for the 4 tiles of a workgroup
-static constexpr int kFcaGroupAtoms = 16;   // (C4 fca: 4 -> 213 us, 8 -> 196, 16 -> 186, 32 -> 199)
-static void fca_plan(const mq_ctx* c, const std::vector<std::vector<uint32_t>>& fm, const std::vector<std::vector<FcCmpH>>& fq,
-                     const std::vector<char>& negated, std::vector<char>& keep, const std::function<uint32_t(size_t)>& out_of,
-                     const std::function<std::pair<uint32_t, uint32_t>(size_t)>& nodes_ops, FcaPlan& P,
-                     const std::function<int32_t(size_t)>& mask_out = nullptr) {
-  const uint32_t zero_row = (uint32_t)(c->var_off_h.empty() ? 0 : c->var_off_h.back() + c->var_nl_h.back());
-  // key: row, source limbs, path (1: the 8-limb path — wide compares, zero-extended reads wider
-  // than 64 bits, unary atoms), accept, compare limbs, then the constant / flip limbs and the
-  // transform steps (atoms of one (row, source limbs, path) form groups)
-  auto atom_key = [](const FcCmpH& h, bool* ng) {
-    *ng = h.accept >= 4;
-    const uint32_t src = h.src_nl ? h.src_nl : h.nl;
-    const uint32_t general = (h.nx > 0 || h.nl > 2 || src > 2) ? 1u : 0u;
-    std::vector<uint32_t> key{h.row, src, general, *ng ? (h.accept ^ 7u) : h.accept, h.nl, h.nx};
-    for (uint32_t l = 0; l < h.nl; l++) {
-      key.push_back(h.c[l]);
-      key.push_back(h.f[l]);
-    }
-    for (uint32_t k = 0; k < h.nx; k++) {
-      key.push_back(h.xf[k].code);
-      key.push_back(h.xf[k].p0);
-      key.push_back(h.xf[k].p1);
-      key.push_back(h.xf[k].p2);
-    }
-    return key;
-  };
-  // the segment being built: its atoms / masks in arrival order, and its tapes' symbolic entries
-  // (kind 0 mask slot, 1 atom; local id; negated)
-  struct Ent {
-    uint32_t kind, id, neg;
-  };
-  std::map<std::vector<uint32_t>, uint32_t> atom_of;
-  std::vector<std::vector<uint32_t>> akeys;
-  std::map<uint32_t, uint32_t> mask_of;
-  std::vector<uint32_t> masks;
-  std::vector<std::vector<Ent>> tl;
-  std::vector<size_t> tsrc;
-  P.chunk_off.assign(1, 0);
-  auto close = [&]() {
-    if (tl.empty()) return;
-    FcaPlanSeg sg{};
-    sg.atom_off = (int)P.atoms.size();
-    sg.n_atoms = (int)akeys.size();
-    sg.group_off = (int)P.groups.size();
-    sg.tape_first = (int)P.tape_out.size();
-    sg.n_tapes = (int)tl.size();
-    sg.chunk_first = (int)P.chunk_off.size() - 1;
-    sg.smask_off = (int)P.stage_masks.size();
-    sg.n_smask = (int)masks.size();
-
-    // atoms ordered by (variable row, limbs): groups
-    std::vector<uint32_t> ord(akeys.size());
-    for (size_t i = 0; i < ord.size(); i++) ord[i] = (uint32_t)i;
-    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
-      for (int f = 0; f < 3; f++)
-        if (akeys[x][f] != akeys[y][f]) return akeys[x][f] < akeys[y][f];
-      return false;
-    });
-    static const uint32_t group_atoms = [] {
-      const char* e = std::getenv("MQ_FCA_GROUP_ATOMS");
-      return e ? (uint32_t)std::max(1, std::atoi(e)) : (uint32_t)kFcaGroupAtoms;
-    }();
-    std::vector<uint32_t> pos(akeys.size());
-    for (size_t r = 0; r < ord.size(); r++) {
-      const std::vector<uint32_t>& key = akeys[ord[r]];
-      pos[ord[r]] = (uint32_t)r;
-      // (a group holds at most kFcaGroupAtoms atoms: the 4 waves take every fourth group, so one
-      // variable's many compares must not land on one wave)
-      if (r == 0 || akeys[ord[r - 1]][0] != key[0] || akeys[ord[r - 1]][1] != key[1] ||
-          akeys[ord[r - 1]][2] != key[2] || P.groups.back().count >= group_atoms) {
-        FcaGroup g{};
-        const uint32_t nl = key[1];
-        for (uint32_t l = 0; l < 8; l++) g.rows[l] = l < nl ? key[0] + l : zero_row;
-        g.first = (uint32_t)r;
-        g.nl = key[2] ? 8u : nl;   // (the kernel's 8-limb path for nl > 2)
-        P.groups.push_back(g);
-      }
-      P.groups.back().count++;
-      FcCmp q{};
-      q.h.slot = 0;
-      const uint32_t cnl = key[4], nx = key[5];
-      q.h.nl = cnl;
-      q.h.accept = key[3];
-      uint32_t cc[8] = {0}, ff[8] = {0};
-      for (uint32_t l = 0; l < cnl; l++) {
-        cc[l] = key[6 + 2 * l];
-        ff[l] = key[7 + 2 * l];
-      }
-      FcXf xf{};
-      xf.n = nx;
-      for (uint32_t k = 0; k < nx; k++) {
-        const size_t o = 6 + 2 * cnl + 4 * k;
-        xf.op[k] = FcXop{key[o], key[o + 1], key[o + 2], key[o + 3]};
-      }
-      P.xfs.push_back(xf);
-      P.any_xf |= nx > 0;
-      q.h.c01 = (uint64_t)cc[0] | ((uint64_t)cc[1] << 32);
-      q.h.f01 = (uint64_t)ff[0] | ((uint64_t)ff[1] << 32);
-      for (int l = 0; l < 6; l++) {
-        q.t.c[l] = cc[2 + l];
-        q.t.f[l] = ff[2 + l];
-      }
-      P.atoms.push_back(q);
-    }
-    sg.n_groups = (int)P.groups.size() - sg.group_off;
-    P.stage_masks.insert(P.stage_masks.end(), masks.begin(), masks.end());
-    const uint32_t abase = 1u + (uint32_t)masks.size();
-    // chunks of 64 tapes, entries k-major; short lists padded with entry 0 (all ones)
-    for (size_t c0 = 0; c0 < tl.size(); c0 += 64) {
-      size_t kmax = 0;
-      for (size_t t = c0; t < std::min(tl.size(), c0 + 64); t++) kmax = std::max(kmax, tl[t].size());
-      for (size_t k = 0; k < kmax; k++)
-        for (size_t l = 0; l < 64; l++) {
-          const size_t t = c0 + l;
-          uint32_t e = 0;
-          if (t < tl.size() && k < tl[t].size()) {
-            const Ent& x = tl[t][k];
-            e = (x.kind == 0 ? 1u + x.id : abase + pos[x.id]) | (x.neg ? 0x80000000u : 0u);
-          }
-          P.lists.push_back(e);
-        }
-      P.chunk_off.push_back((uint32_t)P.lists.size());
-    }
-    for (size_t t = 0; t < tl.size(); t++) {
-      P.tape_out.push_back(out_of(tsrc[t]) | (negated[tsrc[t]] ? 0x80000000u : 0u));
-      const auto no = nodes_ops(tsrc[t]);
-      P.metric.push_back(no.first);
-      P.metric.push_back(no.second);
-      if (mask_out) P.col_mask.push_back(mask_out(tsrc[t]));
-    }
-    P.segs.push_back(sg);
-    atom_of.clear();
-    akeys.clear();
-    mask_of.clear();
-    masks.clear();
-    tl.clear();
-    tsrc.clear();
-  };
-  for (size_t i = 0; i < keep.size(); i++) {
-    if (!keep[i]) continue;
-    if (fq[i].size() > (size_t)kFcaMaxAtoms || fm[i].size() > (size_t)kFcStageMasks) {
-      keep[i] = 0;
-      continue;
-    }
-    // this tape's new atoms / masks; a new segment when they do not fit
-    size_t new_a = 0, new_m = 0;
-    {
-      std::set<std::vector<uint32_t>> fa;
-      std::set<uint32_t> fmk;
-      for (const auto& h : fq[i]) {
-        bool ng;
-        auto key = atom_key(h, &ng);
-        if (!atom_of.count(key)) fa.insert(key);
-      }
-      for (uint32_t e : fm[i])
-        if (!mask_of.count(e & 0x7FFFFFFFu)) fmk.insert(e & 0x7FFFFFFFu);
-      new_a = fa.size();
-      new_m = fmk.size();
-    }
-    if (akeys.size() + new_a > (size_t)kFcaMaxAtoms || masks.size() + new_m > (size_t)kFcStageMasks) close();
-    std::vector<Ent> ent;
-    for (uint32_t e : fm[i]) {
-      const uint32_t v = e & 0x7FFFFFFFu;
-      auto it = mask_of.find(v);
-      uint32_t id;
-      if (it == mask_of.end()) {
-        id = (uint32_t)masks.size();
-        mask_of[v] = id;
-        masks.push_back(v);
-      } else {
-        id = it->second;
-      }
-      ent.push_back(Ent{0, id, e >> 31});
-    }
-    for (const auto& h : fq[i]) {
-      bool ng;
-      auto key = atom_key(h, &ng);
-      auto it = atom_of.find(key);
-      uint32_t id;
-      if (it == atom_of.end()) {
-        id = (uint32_t)akeys.size();
-        atom_of[key] = id;
-        akeys.push_back(key);
-      } else {
-        id = it->second;
-      }
-      ent.push_back(Ent{1, id, ng ? 1u : 0u});
-    }
-    tl.push_back(std::move(ent));
-    tsrc.push_back(i);
-  }
-  close();
-}
-
-// A tape's low-limb prefilter program (CompiledTape::prog_pf) as P entries for frame mode 4:
-// (handler address, the instruction's 32-bit immediate, 0).  PUSH_VAR and the bitwise ops are
-// P's own handlers (on the narrow register map they act on eight blocks' low limbs).
-static bool qsa_translate_pf(const mq_ctx* c, const CompiledTape& x, std::vector<uint32_t>& out) {
-  out.clear();
-  if (x.depth_pf > kQsaStackP) return false;
-  for (size_t pc = 0; pc + 1 < x.prog_pf.size(); pc += 2) {
-    const uint32_t op = x.prog_pf[pc] & 0xFFu, imm = x.prog_pf[pc + 1];
-    const int d = (int)((x.prog_pf[pc] >> 8) & 0xFu);
-    int kind = -1, v = -1;
-    uint32_t im = imm;
-    switch (op) {
-      case PF_END: kind = QK_END; break;
-      case PF_PUSH_VAR:
-        if (imm >= (uint32_t)kQsaVars) return false;
-        kind = QK_PUSH_VAR, v = (int)imm, im = 0;
-        break;
-      case PF_PUSH_K: kind = QK_PUSH_K32; break;
-      case PF_ADD: kind = QK_ADD32; break;
-      case PF_SUB: kind = QK_SUB32; break;
-      case PF_MUL: kind = QK_MUL32; break;
-      case PF_NEG: kind = QK_NEG32; break;
-      case PF_BAND: kind = QK_BAND; break;
-      case PF_BOR: kind = QK_BOR; break;
-      case PF_BXOR: kind = QK_BXOR; break;
-      case PF_BNOT: kind = QK_BNOT; break;
-      case PF_ADDK: kind = QK_ADDK32; break;
-      case PF_MULK: kind = QK_MULK32; break;
-      case PF_ANDK: kind = QK_ANDK32; break;
-      case PF_ORK: kind = QK_ORK32; break;
-      case PF_XORK: kind = QK_XORK32; break;
-      case PF_EQ: kind = QK_EQ32; break;
-      case PF_EQK: kind = QK_EQK32; break;
-      default: return false;
-    }
-    if (d >= kQsaStackP) return false;
-    const int h = c->qsa_index[0][kind][kind == QK_END ? 0 : d][v + 1];
-    if (h < 0) return false;
-    out.push_back(c->qsa_hbase_lo[0] + c->qsa_off[0][h]);
-    out.push_back(im);
-    out.push_back(0);
-  }
-  return !out.empty();
-}
-
 static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   if (T->qsa_gen == c->layout_gen) return MQ_OK;
   T->qsa_gen = c->layout_gen;
@@ -4147,60 +2632,41 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
     parallel_for(nq, 32, [&](int, int64_t b, int64_t e) {
       for (int64_t i = b; i < e; i++) {
         bool ng = false;
-        on_fc[i] = fc_match(c, T->qct[i], fc_m[i], fc_q[i], &ng, unary) ? 1 : 0;
+        on_fc[i] = fc_match(c->layout, T->qct[i], fc_m[i], fc_q[i], &ng, unary) ? 1 : 0;
         fc_neg[i] = ng ? 1 : 0;
       }
     });
   FcPlan fcp;
   FcaPlan fap;
   if (T->fca)
-    fca_plan(c, fc_m, fc_q, fc_neg, on_fc, [&](size_t i) { return T->qbase[i].tape; },
+    fca_plan(c->layout, fc_m, fc_q, fc_neg, on_fc, [&](size_t i) { return T->qbase[i].tape; },
              [&](size_t i) { return std::make_pair(T->qbase[i].n_nodes, T->qbase[i].alg_ops); }, fap);
   else
-    fc_plan(c, fc_m, fc_q, fc_neg, on_fc, [&](size_t i) { return T->qbase[i].tape; }, [](size_t) { return (int32_t)-1; },
+    fc_plan(c->layout, fc_m, fc_q, fc_neg, on_fc, [&](size_t i) { return T->qbase[i].tape; }, [](size_t) { return (int32_t)-1; },
             [&](size_t i) { return std::make_pair(T->qbase[i].n_nodes, T->qbase[i].alg_ops); }, fcp);
-  // (P preloads variables 0-7 only: a program pushing any other variable is not tried on P)
-  auto p_candidate = [](const CompiledTape& x) {
-    for (size_t pc = 0; pc < x.prog.size(); pc++) {
-      const uint32_t op = x.prog[pc] & 0xFFu;
-      if ((op == G_PUSH_VAR || op == G_PUSH_VAR_B) && (x.prog[pc] >> 12) >= (uint32_t)kQsaVars) return false;
-      if (has_imm2(op)) pc++;
-    }
-    return true;
-  };
   // (a latency-bound launch runs everything on G, one tape per wave: no P attempt.  Chunks of
   // 32 tapes: a drop-in batch of a few conjunct tapes is translated on the calling thread, which
   // is cheaper than waking the pool)
   if (!latency)
     parallel_for(nq, 32, [&](int, int64_t b, int64_t e) {
       for (int64_t i = b; i < e; i++)
-        on_p[i] = !on_fc[i] && p_candidate(T->qct[i]) && qsa_translate(c, 0, true, T->qct[i], nullptr, nullptr) ? 1 : 0;
+        on_p[i] = !on_fc[i] && p_candidate(T->qct[i]) && qsa_translate(c->qsa, c->layout, 0, true, T->qct[i], nullptr, nullptr) ? 1 : 0;
     });
-  std::vector<int64_t> pushes(c->var_nl_h.size(), 0);
-  for (size_t i = 0; i < T->qct.size(); i++) {
-    if (on_p[i] || on_fc[i]) continue;
-    const auto& pr = T->qct[i].prog;
-    for (size_t pc = 0; pc < pr.size(); pc++) {
-      const uint32_t op = pr[pc] & 0xFFu, imm = pr[pc] >> 12;
-      // (Bool variables with a lane mask are neither preloaded nor staged: PUSH_PKB)
-      if ((op == G_PUSH_VAR || (op == G_PUSH_VAR_B && !(imm < c->bmask_of_var.size() && c->bmask_of_var[imm] >= 0))) &&
-          imm < pushes.size() && c->var_nl_h[imm] <= 8)
-        pushes[imm]++;
-      if (has_imm2(op)) pc++;
-    }
-  }
+  std::vector<char> not_g(nq, 0);   // the tapes P or the flat kernel takes
+  for (int64_t i = 0; i < nq; i++) not_g[i] = on_p[i] || on_fc[i];
+  const std::vector<int64_t> pushes = count_pushes(c->layout, T->qct, &not_g);
   std::vector<int> order;
   for (size_t v = 0; v < pushes.size(); v++)
     if (pushes[v] > 0) order.push_back((int)v);
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pushes[a] > pushes[b]; });
   if (order.size() > (size_t)kQsaVarsG) order.resize(kQsaVarsG);
-  T->gpre.assign(c->var_nl_h.size(), -1);
-  const uint32_t zero_row = (uint32_t)(c->var_off_h.empty() ? 0 : c->var_off_h.back() + c->var_nl_h.back());
+  T->gpre.assign(c->layout.var_nl.size(), -1);
+  const uint32_t zero_row = c->layout.zero_row();
   for (int j = 0; j < 64; j++) T->g_var_row[j] = zero_row;
   for (size_t j = 0; j < order.size(); j++) {
     const int v = order[j];
     T->gpre[v] = (int)j;
-    for (uint32_t l = 0; l < c->var_nl_h[v]; l++) T->g_var_row[8 * j + l] = c->var_off_h[v] + l;
+    for (uint32_t l = 0; l < c->layout.var_nl[v]; l++) T->g_var_row[8 * j + l] = c->layout.var_off[v] + l;
   }
   int g_temps = 0;
   for (size_t i = 0; i < T->qct.size(); i++)
@@ -4208,7 +2674,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   int64_t n_g = 0;
   for (size_t i = 0; i < T->qct.size(); i++) n_g += (on_p[i] || on_fc[i]) ? 0 : 1;
   const double g_share = n_g ? std::min(1.0, 4.0 * (double)g_tapes_per_group(n_g, c->M) / (double)n_g) : 1.0;
-  plan_stage(c, pushes, &T->gpre, g_temps, g_share, T->gstage, T->stage_rows);
+  plan_stage(c->layout, pushes, &T->gpre, g_temps, g_share, T->gstage, T->stage_rows);
   T->qhist[0].assign(QK_COUNT, 0);
   T->qhist[1].assign(QK_COUNT, 0);
   T->qpairs.assign((size_t)QK_COUNT * QK_COUNT, 0);
@@ -4226,13 +2692,13 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
         kind_of[i] = 2;
         continue;
       }
-      if (on_p[i] && qsa_translate(c, 0, true, T->qct[i], &trs[i], &ex)) continue;
+      if (on_p[i] && qsa_translate(c->qsa, c->layout, 0, true, T->qct[i], &trs[i], &ex)) continue;
       kind_of[i] = 1;
-      if (!qsa_translate(c, 1, true, T->qct[i], &trs[i], &ex, &T->gpre, &T->gstage, g_bail)) {
+      if (!qsa_translate(c->qsa, c->layout, 1, true, T->qct[i], &trs[i], &ex, &T->gpre, &T->gstage, g_bail)) {
         g_fail = true;
         break;
       }
-      qsa_window_layout(c, trs[i]);
+      qsa_window_layout(c->qsa, trs[i]);
     }
   });
   if (g_fail) return MQ_OK;
@@ -4241,7 +2707,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
     const int k = kind_of[i];
     if (k == 2) continue;
     const std::vector<uint32_t>& t = trs[i];
-    qsa_count(c, k, t, T->qhist[k], k == 1 ? &T->qpairs : &T->qpairs_p);
+    qsa_count(c->qsa, k, t, T->qhist[k], k == 1 ? &T->qpairs : &T->qpairs_p);
     GDesc d = T->qbase[i];
     d.prog_off = (uint32_t)words[k].size();
     d.prog_len = (uint32_t)t.size();
@@ -4264,7 +2730,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
     d.prog_off = 0;
     d.prog_len = 0;
     std::vector<uint32_t> t;
-    if (!x.prog_pf.empty() && qsa_translate_pf(c, x, t)) {
+    if (!x.prog_pf.empty() && qsa_translate_pf(c->qsa, x, t)) {
       d.prog_off = (uint32_t)words[0].size();
       d.prog_len = (uint32_t)t.size();
       d.alg_ops = (uint32_t)std::llround(x.pf_alg_ops);
@@ -4293,11 +2759,11 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
       descs.push_back(d);
     }
     prog.insert(prog.end(), words[k].begin(), words[k].end());
-    const uint32_t endo = c->qsa_off[k][c->qsa_index[k][QK_END][0][0]];
+    const uint32_t endo = c->qsa.off[k][c->qsa.index[k][QK_END][0][0]];
     const uint32_t endw = hword(1, endo);
     if (k == 0) {   // P entries are (handler address, imm, prefetch); the x4 entry load reads one more word
       for (int r = 0; r < 2; r++) {
-        prog.push_back(c->qsa_hbase_lo[0] + endo);
+        prog.push_back(c->qsa.hbase_lo[0] + endo);
         prog.push_back(0);
         prog.push_back(0);
       }
@@ -4323,11 +2789,7 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
     T->fca_segs = fap.segs;
     T->fca_any_xf = fap.any_xf;
     if (T->fc_count > 0) {
-      if (fap.stage_masks.empty()) fap.stage_masks.push_back(0);
-      if (fap.atoms.empty()) fap.atoms.push_back(FcCmp{});
-      if (fap.xfs.empty()) fap.xfs.push_back(FcXf{});
-      if (fap.groups.empty()) fap.groups.push_back(FcaGroup{});
-      if (fap.lists.empty()) fap.lists.push_back(0);
+      fap.pad_empty();
       pk.add(T->fc_cmp_dev, fap.atoms.data(), fap.atoms.size());
       pk.add(T->fca_xf_dev, fap.xfs.data(), fap.xfs.size());
       pk.add(T->fca_group_dev, fap.groups.data(), fap.groups.size());
@@ -4364,52 +2826,6 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   T->qargs_valid[0] = T->qargs_valid[1] = T->qargs_valid[2] = false;
   T->qsa_live = true;
   return MQ_OK;
-}
-
-// Latency weight of a G program on one tile: its ops, plus the round trips of its variable
-// pushes and table lookups (a store chain's select ends in a lookup; these dominate a column level)
-static double g_cost(const CompiledTape& x) {
-  double w = 0;
-  for (size_t pc = 0; pc < x.prog.size(); pc++) {
-    const uint32_t op = x.prog[pc] & 0xFFu;
-    w += 1;
-    if (op == G_PUSH_VAR || op == G_PUSH_VAR_B) w += 4;
-    if (op == G_UF1 || op == G_UF2 || op == G_UFK0 || op == G_UFK || op == G_UFKV) w += 24;
-    if (has_imm2(op)) pc++;
-  }
-  return w;
-}
-
-// Split a column level's G programs into groups (a group = one wave of G on one tile; group g
-// = descriptors [tab[g], tab[g+1]), the table gen_qsa.py's mode-3 prologue reads) so the
-// heaviest group is as light as it can be: longest processing time first over
-// min(n, ceil(n / tpg) rounded up to the workgroup's 4 waves) groups, of any sizes.  A workgroup
-// holds its LDS until its slowest wave ends, so a level's time follows its heaviest group (C4
-// level 2, five store chains: three in one wave of three 0.69 ms; 2-2-1 0.50 ms).  Reorders idx
-// group by group; tab gets groups rounded up to 4, + 1 entries (empty groups past the last).
-static void balance_groups(const std::vector<CompiledTape>& ct, std::vector<int>& idx, int tpg,
-                           std::vector<uint32_t>& tab) {
-  const int n = (int)idx.size();
-  const int groups = std::max(1, std::min(n, ((n + tpg - 1) / tpg + 3) / 4 * 4));
-  std::vector<std::pair<double, int>> w;
-  for (int i : idx) w.push_back({g_cost(ct[i]), i});
-  std::stable_sort(w.begin(), w.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-  std::vector<double> load(groups, 0);
-  std::vector<std::vector<int>> members(groups);
-  for (const auto& x : w) {
-    int best = 0;
-    for (int g = 1; g < groups; g++)
-      if (load[g] < load[best]) best = g;
-    members[best].push_back(x.second);
-    load[best] += x.first;
-  }
-  idx.clear();
-  tab.assign(1, 0);
-  for (const auto& m : members) {
-    idx.insert(idx.end(), m.begin(), m.end());
-    tab.push_back((uint32_t)idx.size());
-  }
-  while ((tab.size() - 1) % 4) tab.push_back((uint32_t)n);
 }
 
 // Translate the G-eligible column programs for the current model batch (variable rows): one
@@ -4453,11 +2869,11 @@ static int cq_prepare(mq_ctx* c, mq_tapes* T) {
     if (!no_flat)
       for (int i = 0; i < n0; i++) {
         bool ng = false;
-        on_fc[i] = T->cq_bool[b + i] && fc_match(c, T->cq_ct[b + i], fm[i], fq[i], &ng) ? 1 : 0;
+        on_fc[i] = T->cq_bool[b + i] && fc_match(c->layout, T->cq_ct[b + i], fm[i], fq[i], &ng) ? 1 : 0;
         fneg[i] = ng ? 1 : 0;
       }
     FcaPlan fap;
-    fca_plan(c, fm, fq, fneg, on_fc, [&](size_t i) { return c->var_off_h[T->cq_var[b + i]]; },
+    fca_plan(c->layout, fm, fq, fneg, on_fc, [&](size_t i) { return c->layout.var_off[T->cq_var[b + i]]; },
              [&](size_t i) {
                const CompiledTape& x = T->cq_ct[b + i];
                return std::make_pair(x.n_nodes, (uint32_t)std::min(x.alg_ops, 4.0e9));
@@ -4465,18 +2881,14 @@ static int cq_prepare(mq_ctx* c, mq_tapes* T) {
              fap,
              [&](size_t i) {
                const int v = T->cq_var[b + i];
-               return (int32_t)(v < (int)c->bmask_of_var.size() ? c->bmask_of_var[v] : -1);
+               return (int32_t)(v < (int)c->layout.bmask_of_var.size() ? c->layout.bmask_of_var[v] : -1);
              });
     mq_tapes::FcLevel& fl = *T->fc_lvl[li];
     fl.count = (int)fap.tape_out.size();
     fl.segs = fap.segs;
     fl.any_xf = fap.any_xf;
     if (fl.count > 0) {
-      if (fap.stage_masks.empty()) fap.stage_masks.push_back(0);
-      if (fap.atoms.empty()) fap.atoms.push_back(FcCmp{});
-      if (fap.xfs.empty()) fap.xfs.push_back(FcXf{});
-      if (fap.groups.empty()) fap.groups.push_back(FcaGroup{});
-      if (fap.lists.empty()) fap.lists.push_back(0);
+      fap.pad_empty();
       HIPCHK(fl.atoms.upload(fap.atoms.data(), fap.atoms.size(), c->stream));
       HIPCHK(fl.xfs.upload(fap.xfs.data(), fap.xfs.size(), c->stream));
       HIPCHK(fl.groups.upload(fap.groups.data(), fap.groups.size(), c->stream));
@@ -4507,25 +2919,25 @@ static int cq_prepare(mq_ctx* c, mq_tapes* T) {
     const double share = std::min(1.0, 4.0 * (double)cq_tapes_per_group(n, c->M) / (double)n);
     std::vector<int> gstage;
     std::vector<uint32_t> rows;
-    plan_stage(c, count_pushes(c, lvl), nullptr, temps, share, gstage, rows);
+    plan_stage(c->layout, count_pushes(c->layout, lvl), nullptr, temps, share, gstage, rows);
     T->cq_lvl_stage_off[li] = (uint32_t)T->cq_stage_rows.size();
     T->cq_lvl_stage_n[li] = (uint32_t)rows.size();
     T->cq_lvl_temps[li] = temps;
     T->cq_stage_rows.insert(T->cq_stage_rows.end(), rows.begin(), rows.end());
     for (int i : rest) {
       const CompiledTape& x = T->cq_ct[i];
-      if (!qsa_translate(c, 1, true, x, &tr, &extra, nullptr, &gstage)) return MQ_OK;
-      qsa_count(c, 1, tr, T->qhist[2], nullptr);
+      if (!qsa_translate(c->qsa, c->layout, 1, true, x, &tr, &extra, nullptr, &gstage)) return MQ_OK;
+      qsa_count(c->qsa, 1, tr, T->qhist[2], nullptr);
       const int v = T->cq_var[i];
       GDesc d{};
       d.prog_len = (uint32_t)tr.size();
-      d.prog_off = pack_block ? (qsa_window_layout(c, tr), (uint32_t)prog.size()) : qsa_pack_program(c, prog, pack_pos, tr);
-      d.tape = c->var_off_h[v];
+      d.prog_off = pack_block ? (qsa_window_layout(c->qsa, tr), (uint32_t)prog.size()) : qsa_pack_program(c->qsa, prog, pack_pos, tr);
+      d.tape = c->layout.var_off[v];
       d.const_base = (uint32_t)consts.size();
       d.n_nodes = x.n_nodes;
-      d.n_temps = c->var_nl_h[v];
+      d.n_temps = c->layout.var_nl[v];
       // Bool root: bit 0, and the packed lane-mask index + 1 above it (store_column)
-      d.depth = T->cq_bool[i] ? 1u | ((uint32_t)(v < (int)c->bmask_of_var.size() ? c->bmask_of_var[v] + 1 : 0) << 1) : 0u;
+      d.depth = T->cq_bool[i] ? 1u | ((uint32_t)(v < (int)c->layout.bmask_of_var.size() ? c->layout.bmask_of_var[v] + 1 : 0) << 1) : 0u;
       d.alg_ops = (uint32_t)std::min(x.alg_ops, 4.0e9);
       if (pack_block) prog.insert(prog.end(), tr.begin(), tr.end());
       consts.insert(consts.end(), x.consts.begin(), x.consts.end());
@@ -4533,7 +2945,7 @@ static int cq_prepare(mq_ctx* c, mq_tapes* T) {
       descs.push_back(d);
     }
   }
-  const uint32_t endw = hword(1, c->qsa_off[1][c->qsa_index[1][QK_END][0][0]]);
+  const uint32_t endw = hword(1, c->qsa.off[1][c->qsa.index[1][QK_END][0][0]]);
   if (pack_pos) prog.insert(prog.end(), 64 - pack_pos, endw);   // (whole blocks)
   prog.insert(prog.end(), 130, endw);   // the window + next-window prefetch read up to 127 words past the last END
   consts.resize(consts.size() + 16, 0);
@@ -4669,7 +3081,7 @@ static int launch_all(mq_ctx* c, mq_tapes* T, int32_t* best, uint8_t* verdicts, 
   // hoisted columns first (they write model variable rows the tapes read)
   for (size_t i = 0; i < T->col_var.size(); i++) {
     const int v = T->col_var[i];
-    if (v < 0 || v >= c->n_vars || nl_of(c->var_width[v]) != nl_of(T->col_width[i])) {
+    if (v < 0 || v >= c->n_vars || nl_of(c->layout.var_width[v]) != nl_of(T->col_width[i])) {
       g_last_error = "column target variable does not match the uploaded model batch";
       return MQ_ERR_ARG;
     }
@@ -4689,7 +3101,7 @@ static int launch_all(mq_ctx* c, mq_tapes* T, int32_t* best, uint8_t* verdicts, 
     HIPCHK(hipEventRecord(c->stage_ev, c->stream));
     HIPCHK(hipStreamWaitEvent(st, c->stage_ev, 0));
   }
-  const uint32_t zero_row = (uint32_t)(c->var_off_h.empty() ? 0 : c->var_off_h.back() + c->var_nl_h.back());
+  const uint32_t zero_row = c->layout.zero_row();
   if (T->bmask_gen != c->layout_gen) {
     // the mask indices of each level's Bool columns under this model batch
     T->lvl_bmask_h.assign(T->clevels.size(), {});
@@ -4699,11 +3111,11 @@ static int launch_all(mq_ctx* c, mq_tapes* T, int32_t* best, uint8_t* verdicts, 
       if (v >= 0 && v < c->n_vars) on_g[v] = 1;
     for (size_t i = 0; i < T->col_var.size(); i++) {
       const int v = T->col_var[i];
-      if (T->col_width[i] == 0 && v < (int)c->bmask_of_var.size() && c->bmask_of_var[v] >= 0 &&
+      if (T->col_width[i] == 0 && v < (int)c->layout.bmask_of_var.size() && c->layout.bmask_of_var[v] >= 0 &&
           T->col_level[i] < (int)T->clevels.size()) {
         const bool direct = i < T->col_direct_mask.size() && T->col_direct_mask[i];   // the keccak kernel stores it
-        if (!direct) T->lvl_bmask_h[T->col_level[i]].push_back(c->bmask_of_var[v]);
-        if (!on_g[v] && !direct) T->lvl_bmask_cpp_h[T->col_level[i]].push_back(c->bmask_of_var[v]);
+        if (!direct) T->lvl_bmask_h[T->col_level[i]].push_back(c->layout.bmask_of_var[v]);
+        if (!on_g[v] && !direct) T->lvl_bmask_cpp_h[T->col_level[i]].push_back(c->layout.bmask_of_var[v]);
       }
     }
     T->lvl_bmask.resize(T->clevels.size());
@@ -4723,36 +3135,36 @@ static int launch_all(mq_ctx* c, mq_tapes* T, int32_t* best, uint8_t* verdicts, 
     std::vector<KcMapEntry> map;
     std::vector<KcPred> preds;
     for (const auto& h : T->kc) {
-      if (h.target < 0 || h.target >= c->n_vars || c->var_nl_h[h.target] != 8) {
+      if (h.target < 0 || h.target >= c->n_vars || c->layout.var_nl[h.target] != 8) {
         g_last_error = "keccak column target is not a 256-bit variable of the uploaded model batch";
         return MQ_ERR_ARG;
       }
       KcCol kc{};
       kc.map_off = (uint32_t)map.size();
-      kc.target_row = c->var_off_h[h.target];
+      kc.target_row = c->layout.var_off[h.target];
       kc.n_nodes = h.n_nodes;
       kc.alg_ops = h.alg_ops;
       for (const auto& p : h.pieces) {
-        if (p.var >= 0 && (p.var >= c->n_vars || c->var_nl_h[p.var] != p.nl)) {
+        if (p.var >= 0 && (p.var >= c->n_vars || c->layout.var_nl[p.var] != p.nl)) {
           g_last_error = "keccak column piece does not match the uploaded model batch";
           return MQ_ERR_ARG;
         }
         for (int l = (int)p.nl - 1; l >= 0; l--)
-          map.push_back(p.var >= 0 ? KcMapEntry{c->var_off_h[p.var] + (uint32_t)l, 0u}
+          map.push_back(p.var >= 0 ? KcMapEntry{c->layout.var_off[p.var] + (uint32_t)l, 0u}
                                    : KcMapEntry{~0u, T->kc_consts[p.coff + (uint32_t)l]});
       }
       kc.nwords = (uint32_t)map.size() - kc.map_off;
       kc.pred_off = (uint32_t)preds.size();
       for (const auto& ph : h.preds) {
-        if (ph.target < 0 || ph.target >= c->n_vars || c->var_width[ph.target] != 0) {
+        if (ph.target < 0 || ph.target >= c->n_vars || c->layout.var_width[ph.target] != 0) {
           g_last_error = "keccak predicate column target is not a Bool variable of the uploaded model batch";
           return MQ_ERR_ARG;
         }
         KcPred kp{};
         kp.kind = ph.kind;
         kp.bits = ph.bits;
-        kp.row = c->var_off_h[ph.target];
-        kp.mask = ph.target < (int)c->bmask_of_var.size() ? c->bmask_of_var[ph.target] : -1;
+        kp.row = c->layout.var_off[ph.target];
+        kp.mask = ph.target < (int)c->layout.bmask_of_var.size() ? c->layout.bmask_of_var[ph.target] : -1;
         std::memcpy(kp.c, ph.c, sizeof(kp.c));
         preds.push_back(kp);
       }
@@ -4772,22 +3184,22 @@ static int launch_all(mq_ctx* c, mq_tapes* T, int32_t* best, uint8_t* verdicts, 
     std::vector<CwCol> cols;
     std::vector<CwChunk> chunks;
     auto row_of = [&](int32_t v, uint32_t l) -> uint32_t {
-      return (v >= 0 && v < c->n_vars && l < c->var_nl_h[v]) ? c->var_off_h[v] + l : zero_row;
+      return (v >= 0 && v < c->n_vars && l < c->layout.var_nl[v]) ? c->layout.var_off[v] + l : zero_row;
     };
     for (const auto& h : T->cw) {
       const uint32_t nl = (uint32_t)h.limb_slots.size();
-      if (h.target < 0 || h.target >= c->n_vars || c->var_nl_h[h.target] != nl) {
+      if (h.target < 0 || h.target >= c->n_vars || c->layout.var_nl[h.target] != nl) {
         g_last_error = "bit-gather column target does not match the uploaded model batch";
         return MQ_ERR_ARG;
       }
-      if (h.size_var >= 0 && (h.size_var >= c->n_vars || c->var_nl_h[h.size_var] != 8)) {
+      if (h.size_var >= 0 && (h.size_var >= c->n_vars || c->layout.var_nl[h.size_var] != 8)) {
         g_last_error = "bit-gather column size variable is not a 256-bit variable of the uploaded model batch";
         return MQ_ERR_ARG;
       }
       CwCol col{};
       col.chunk_off = (uint32_t)chunks.size();
-      col.target_row = c->var_off_h[h.target];
-      col.size_row = h.size_var >= 0 ? c->var_off_h[h.size_var] : ~0u;
+      col.target_row = c->layout.var_off[h.target];
+      col.size_row = h.size_var >= 0 ? c->layout.var_off[h.size_var] : ~0u;
       col.n_nodes = h.n_nodes;
       col.alg_ops = h.alg_ops;
       for (uint32_t l = 0; l < nl; l++) {

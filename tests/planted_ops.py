@@ -16,7 +16,7 @@ shares no code with the oracles, which the grid therefore checks as well.
 
 An operand is a model variable ("v"), a constant of at most 16 bits ("k"), a wider constant
 ("K") or a computed sub-term ("c": ``BXOR(var, const)`` with the variable planted so that the
-sub-term has the wanted value) - the operand forms the assembly translator (mq_api.cpp
+sub-term has the wanted value) - the operand forms the assembly translator (qsa_translate.cpp
 qsa_translate) picks different handlers for.  Every case whose widest value has 256 bits, and
 every narrower case at operand widths 33 and 160, exists twice: with its variables at indices below
 8 (the P kernel's preloaded set, ``place == "lo"``; 8 variables a batch, so these come in many small

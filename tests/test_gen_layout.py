@@ -58,7 +58,7 @@ def test_product_g_is_the_compact_layout():
 def test_g_handler_data_words_match_their_kinds():
     """kQsaHandlerDataWordsG (counted from each handler body's window reads) gives every
     handler that carries inline words the count its translator form emits: a handler whose data
-    is mis-counted would be split from its data by the window layout (mq_api.cpp
+    is mis-counted would be split from its data by the window layout (qsa_translate.cpp
     qsa_window_layout) and read a wild mask index / constant."""
     tab = open(os.path.join(os.path.dirname(INC), "qsa_table.h")).read()
     keys = re.findall(r"\{QK_(\w+), (-?\d+), (-?\d+)\}", tab[tab.index("kQsaHandlerKeysG"):])

@@ -1,5 +1,5 @@
 """Bail points on the general assembly interpreter (MQ_G_BAIL=1; gen_qsa.py G BAIL handler,
-mq_api.cpp qsa_translate): a wave that leaves a tape mid-window decides what the oracle decides
+qsa_translate.cpp qsa_translate): a wave that leaves a tape mid-window decides what the oracle decides
 and leaves the next tape of its group intact -- first hits and verdicts integer-exact against
 ``cref`` with the flag on and off -- and the counters say what ran.  (The skipped-ops count of a
 bail word is a word of the tape's constants, not an inline data word: what must not straddle a

@@ -1588,7 +1588,7 @@ def _unary_atom_workload(seed, n_tapes=160, M=700):
 
 @pytest.mark.parametrize("seed", range(4))
 def test_flat_unary_atoms_match_oracle(evaluator, monkeypatch, seed):
-    """fca_kernel's unary atoms (fc.hip fx_apply; mq_api.cpp fc_match with unary steps; opt-in
+    """fca_kernel's unary atoms (fc.hip fx_apply; fc_plan.cpp fc_match with unary steps; opt-in
     MQ_FC_UNARY=1): the workload's tapes run on the flat kernel, and their verdicts and first
     hits are the oracle's (and the direct term evaluator's)."""
     import term_eval

@@ -16,8 +16,8 @@ FLAT_BOOL = {("NOT", "v"), ("AND", "vT"), ("AND", "vv"), ("OR", "vv")}
 
 
 def expected_kernel(c: pl.LCase) -> str:
-    """Which kernel runs a case on the default path, read from the translator (mq_api.cpp
-    qsa_translate / qsa_prepare, tape_compiler.cpp) and confirmed on the MI355X:
+    """Which kernel runs a case on the default path, read from the translator (qsa_translate.cpp
+    qsa_translate, mq_api.cpp qsa_prepare, tape_compiler.cpp) and confirmed on the MI355X:
 
     WIDE  a key or result wider than 256 bits, and every in-tape KECCAK: the wider generic HIP C++
           kernels (L = 16 / 32 / 64);

@@ -15,8 +15,8 @@ CMP = (Op.EQ, Op.ULT, Op.ULE, Op.SLT, Op.SLE)
 
 
 def expected_kernel(c: po.Case) -> str:
-    """Which kernel runs a case on the default path, read from the translator (mq_api.cpp
-    qsa_translate / qsa_prepare, tape_compiler.cpp) and confirmed on the MI355X:
+    """Which kernel runs a case on the default path, read from the translator (qsa_translate.cpp
+    qsa_translate, mq_api.cpp qsa_prepare, tape_compiler.cpp) and confirmed on the MI355X:
 
     WIDE  a value wider than 256 bits: the wider generic HIP C++ kernels (L = 16 / 32 / 64);
     CPP   the 256-bit HIP C++ interpreter: the multiplication-overflow predicates (no assembly
