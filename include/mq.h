@@ -543,8 +543,9 @@ int mq_tapes_column_keccak(mq_tapes* tapes, int32_t* n_keccak_columns);
 int mq_tapes_column_keccak_predicates(mq_tapes* tapes, int32_t* n_predicate_columns);
 
 /* After a launch: handler-kind histogram of the current assembly translation (which = 0: P
-   tapes, 1: G tapes, 2: G column programs) into hist_out[cap]; each tape's program runs once per
-   (tape, model) pair, so these are the dispatches per pair summed over tapes.  pairs_out
+   tapes, 1: G tapes, 2: G column programs, 3: the P tapes' low-limb prefilter programs) into
+   hist_out[cap]; each tape's program runs once per (tape, model) pair (a prefilter program once
+   per 512 models), so these are the dispatches per pair summed over tapes.  pairs_out
    (cap x cap, may be NULL): (kind, next kind) counts over the G tapes (which = 1, else zeros).
    *n_kinds_out = number of kinds.  Diagnostic (superinstruction planning).  Returns 0 or
    MQ_ERR_ARG. */
@@ -604,6 +605,11 @@ int mq_tape_prefilter_program(const mq_tape_batch* batch, int32_t t, uint32_t* w
    does from 4096 models of a device's shard on; MQ_PREFILTER=force always, =0 never; never for
    verdicts or a latency-bound launch).  Each may be NULL. */
 int mq_tapes_prefilter_split(mq_tapes* tapes, int32_t* n_prefiltered, int32_t* ran);
+
+/* Over the prefilter programs counted by mq_tapes_prefilter_split: *entries = dispatches of their
+   translation (a fused entry serves several instructions; MQ_PF_FUSE=0: one each), *instrs =
+   instructions of the compiled programs; neither counts the final END.  Each may be NULL. */
+int mq_tapes_prefilter_entries(mq_tapes* tapes, int64_t* entries, int64_t* instrs);
 
 /* Diagnostic: the (block, descriptor) bitmap the last launch's prefilter left on the lead device,
    *rows = ceil(M / 64) rows of *words_per_row words into words[cap_words] (nothing copied when

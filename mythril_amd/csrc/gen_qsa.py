@@ -14,8 +14,9 @@ Two variants are generated from the same handler code (one asm statement each, l
   P ("preload", qsa_kernel):  the wave's 64 models' first 8 variables are preloaded into VGPRs
      once per workgroup; PUSH_VAR is a register copy.  C2-shaped batches.
      Frame mode 4 (pf_frame, behind the handlers) is the low-limb prefilter: the same register
-     map holds limb 0 of eight 64-model blocks, narrow handlers (ADD32 .. EQK32, the last ones)
-     run a tape's cheapest EQ conjunct at 32 bits and a (block, tape) bitmap keeps what survives;
+     map holds limb 0 of eight 64-model blocks, narrow handlers (ADD32 .. EQK32 and their fused
+     forms ADD32V .. MUL32VV, the last ones; tail NEXT_PF) run a tape's cheapest EQ conjunct at
+     32 bits and a (block, tape) bitmap keeps what survives;
      in first-hit mode with that bitmap (QArgs.alive) a wave runs only its block's live tapes
      (alive_scan).
   G ("general", qsg_kernel):  variables pushed from the model rows in HBM (PUSH_MEM: the loads
@@ -194,6 +195,10 @@ NEXT_P = [
     "s_add_u32 s16, s16, 12",
     "s_setpc_b64 s[18:19]",
 ]
+# The narrow handlers of the prefilter mode (frame mode 4) read no constant from CB: their tail
+# is NEXT_P without the constant prefetch.  Both tails consume the same three-word entries, so
+# the mode's programs mix them with P's own handlers (PUSH_VAR, the bitwise ops: NEXT_P).
+NEXT_PF = [ln for ln in NEXT_P if not ln.startswith("s_load_dwordx8")]
 
 
 _WIN_LABELS = [0]
@@ -1229,11 +1234,11 @@ def make_handlers(variant, pfx):
     hs = []
     acc = []   # (key, body without the dispatch tail) of the Bool producers that get _A/_O forms
 
-    def H(key, body, tail=True, reads_stack=True):
+    def H(key, body, tail=True, reads_stack=True, narrow=False):
         pre = [VMWAIT] if (G and reads_stack) else []
         prof = prof_point(key[0]) if G else []
         if tail:
-            hs.append((key, pre + list(body) + prof + (NEXT_G if G else NEXT_P)))
+            hs.append((key, pre + list(body) + prof + (NEXT_G if G else NEXT_PF if narrow else NEXT_P)))
             if pre:
                 hs.append(((key[0] + "_L",) + tuple(key[1:]), [LGKMWAIT] + list(body) + prof_point(key[0] + "_L") + NEXT_G))
         else:
@@ -1671,22 +1676,61 @@ def make_handlers(variant, pfx):
         # within s_branch's reach.
         for d in range(1, D):
             a = d - 1
-            H(("ADD32", d), [f"v_add_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)])
-            H(("SUB32", d), [f"v_sub_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)])
-            H(("MUL32", d), [f"v_mul_lo_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)])
+            H(("ADD32", d), [f"v_add_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)], narrow=True)
+            H(("SUB32", d), [f"v_sub_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)], narrow=True)
+            H(("MUL32", d), [f"v_mul_lo_u32 {S(a, l)}, {S(a, l)}, {S(d, l)}" for l in range(L)], narrow=True)
         for d in range(D):
-            H(("NEG32", d), [f"v_sub_u32 {S(d, l)}, 0, {S(d, l)}" for l in range(L)])
-            H(("PUSH_K32", d), [f"v_mov_b32 {S(d, l)}, s17" for l in range(L)], reads_stack=False)
-            H(("ADDK32", d), [f"v_add_u32 {S(d, l)}, s17, {S(d, l)}" for l in range(L)])
-            H(("MULK32", d), [f"v_mul_lo_u32 {S(d, l)}, {S(d, l)}, s17" for l in range(L)])
+            H(("NEG32", d), [f"v_sub_u32 {S(d, l)}, 0, {S(d, l)}" for l in range(L)], narrow=True)
+            H(("PUSH_K32", d), [f"v_mov_b32 {S(d, l)}, s17" for l in range(L)], reads_stack=False, narrow=True)
+            H(("ADDK32", d), [f"v_add_u32 {S(d, l)}, s17, {S(d, l)}" for l in range(L)], narrow=True)
+            H(("MULK32", d), [f"v_mul_lo_u32 {S(d, l)}, {S(d, l)}, s17" for l in range(L)], narrow=True)
             for nm, ins in (("ANDK32", "v_and_b32"), ("ORK32", "v_or_b32"), ("XORK32", "v_xor_b32")):
-                H((nm, d), [f"{ins} {S(d, l)}, s17, {S(d, l)}" for l in range(L)])
+                H((nm, d), [f"{ins} {S(d, l)}, s17, {S(d, l)}" for l in range(L)], narrow=True)
         # (a VALU write of an SGPR is read by the SALU after >= 4 wait states: s_nop 3)
         pf_and = ["s_nop 3"] + [f"s_and_b64 {PF_R[l]}, {PF_R[l]}, {PF_VM[l]}" for l in range(L)] + [f"s_branch {pfx}_pf_tape_end"]
         for d in range(1, D):
             H(("EQ32", d), [f"v_cmp_eq_u32_e64 {PF_R[l]}, {S(d - 1, l)}, {S(d, l)}" for l in range(L)] + pf_and, tail=False)
         for d in range(D):
             H(("EQK32", d), [f"v_cmp_eq_u32_e64 {PF_R[l]}, s17, {S(d, l)}" for l in range(L)] + pf_and, tail=False)
+        # ---- fused narrow handlers (qsa_translate_pf's peephole): a PUSH_VAR whose only reader is
+        # the next instruction is not dispatched, the reader takes V[v][l] = limb 0 of variable v
+        # in block l in place.  (BANDV / BANDVV and their kin above are limb-wise and serve the
+        # narrow map as they are.)  Behind every older handler, which all keep their offsets.
+        #   kind32V  (d, v):   S[d-1] = S[d-1] op V[v]            EQ32V (d = 1) ends the program like EQ32
+        #   kind32VV (x, v1):  S[x] = V[v1] op V[v2]              imm = 8 * v2, through M0 as ADDVV
+        #   kindK32V (d, v):   S[d] = V[v] op k                   imm = k; EQK32V (d = 0) ends the program
+        # The constant forms are keyed by the variable: the entry's third word is not kept by
+        # NEXT_P, the tail of the shared handlers that may precede them, and indexing through M0
+        # would add a third scalar move to every tail of the mode and two s_set_gpr_idx to the body.
+        # Slots: a narrow program has at most 48 instructions (gprog.h kPfMaxInstr), and the tape
+        # compiler evaluates the deeper operand first, so a value at slot s has 2^s leaves before
+        # it: no program reaches slot 5, and none is generated for it (the translator leaves a
+        # pattern without a handler unfused).
+        DF = D - 1
+        for v in range(NV):
+            def vl(l, v=v):
+                return f"v{VBASE + 8 * v + l}"
+            for d in range(1, DF):
+                a = d - 1
+                H(("ADD32V", d, v), [f"v_add_u32 {S(a, l)}, {S(a, l)}, {vl(l)}" for l in range(L)], narrow=True)
+                H(("SUB32V", d, v), [f"v_sub_u32 {S(a, l)}, {S(a, l)}, {vl(l)}" for l in range(L)], narrow=True)
+                H(("MUL32V", d, v), [f"v_mul_lo_u32 {S(a, l)}, {S(a, l)}, {vl(l)}" for l in range(L)], narrow=True)
+                if d == 1:   # (the final EQ finds nothing below its operands)
+                    H(("EQ32V", d, v), [f"v_cmp_eq_u32_e64 {PF_R[l]}, {S(a, l)}, {vl(l)}" for l in range(L)] + pf_and, tail=False)
+            for d in range(DF):
+                H(("ADDK32V", d, v), [f"v_add_u32 {S(d, l)}, s17, {vl(l)}" for l in range(L)], reads_stack=False, narrow=True)
+                H(("MULK32V", d, v), [f"v_mul_lo_u32 {S(d, l)}, {vl(l)}, s17" for l in range(L)], reads_stack=False, narrow=True)
+                for nm, ins in (("ANDK32V", "v_and_b32"), ("ORK32V", "v_or_b32"), ("XORK32V", "v_xor_b32")):
+                    H((nm, d, v), [f"{ins} {S(d, l)}, s17, {vl(l)}" for l in range(L)], reads_stack=False, narrow=True)
+                if d == 0:
+                    H(("EQK32V", d, v), [f"v_cmp_eq_u32_e64 {PF_R[l]}, s17, {vl(l)}" for l in range(L)] + pf_and, tail=False,
+                      reads_stack=False)
+            # (M0 index mode is on only around the eight VALU and off before the tail, as in ADDVV)
+            on1, off = ["s_set_gpr_idx_on s17, gpr_idx(SRC1)"], ["s_set_gpr_idx_off"]
+            for x in range(DF - 1):
+                for nm, ins in (("ADD32VV", "v_add_u32"), ("SUB32VV", "v_sub_u32"), ("MUL32VV", "v_mul_lo_u32")):
+                    H((nm, x, v), on1 + [f"{ins} {S(x, l)}, {vl(l)}, v{VBASE + l}" for l in range(L)] + off,
+                      reads_stack=False, narrow=True)
     subs = sub_abs_cneg(pfx) + sub_udiv32(pfx) + (sub_uf1(pfx) + sub_udivv(pfx) if G else [])
     return hs, subs
 
@@ -1817,7 +1861,7 @@ def pf_frame(pfx):
           "s_load_dwordx4 s[96:99], s[14:15], 0x0",
           "s_mov_b32 s16, 12",
           "s_mov_b32 s78, s84",
-          "s_mov_b32 s79, s87"] + NEXT_P
+          "s_mov_b32 s79, s87"] + NEXT_PF
     P += [f"{pfx}_pf_tape_end:",
           "s_waitcnt lgkmcnt(0)",                        # the entry and constant prefetches in flight
           "s_add_u32 s40, s40, 1",

@@ -480,9 +480,9 @@ struct mq_tapes {
   std::vector<uint32_t> stage_rows;
   DevBuf stage_dev;
   // handler-kind histograms of the current translation (mq_tapes_qsa_histogram): [0] P tapes,
-  // [1] G tapes, [2] G column programs; qpairs = (kind, next kind) counts over the G tapes,
-  // qpairs_p over the P tapes
-  std::vector<int64_t> qhist[3], qpairs, qpairs_p;
+  // [1] G tapes, [2] G column programs, [3] the P tapes' prefilter programs; qpairs = (kind, next
+  // kind) counts over the G tapes, qpairs_p over the P tapes
+  std::vector<int64_t> qhist[4], qpairs, qpairs_p;
   DevBuf qdescs, qprog, qargs[3];   // [2]: the prefilter launch's (P, mode 4)
   QArgs qargs_dev_copy[3];   // what qargs[k] currently holds on the device
   bool qargs_valid[3] = {false, false, false};
@@ -491,6 +491,8 @@ struct mq_tapes {
   // (block, descriptor) bitmap a launch fills; pf_count = P tapes with a prefilter program
   DevBuf pf_descs, pf_static, pf_alive;
   int pf_count = 0, pf_words = 0;
+  // over those programs: entries of the translation and instructions of prog_pf (END not counted)
+  int64_t pf_entries = 0, pf_instrs = 0;
   bool pf_ran = false;        // the last launch ran the prefilter
   int64_t pf_rows = 0;        // bitmap rows of that launch
   std::vector<int32_t> pf_tape;   // per P descriptor: its tape, and whether it has a prefilter program
@@ -2721,6 +2723,8 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
   std::vector<GDesc> pf_ds(ds[0].size());
   std::vector<uint32_t> pf_static((ds[0].size() + 31) / 32 + 1, 0u);
   T->pf_count = 0;
+  T->pf_entries = T->pf_instrs = 0;
+  T->qhist[3].assign(QK_COUNT, 0);
   T->pf_tape.clear();
   T->pf_has.clear();
   T->pf_words = (int)((ds[0].size() + 31) / 32);
@@ -2735,6 +2739,9 @@ static int qsa_prepare(mq_ctx* c, mq_tapes* T, bool latency) {
       d.prog_len = (uint32_t)t.size();
       d.alg_ops = (uint32_t)std::llround(x.pf_alg_ops);
       words[0].insert(words[0].end(), t.begin(), t.end());
+      qsa_count(c->qsa, 0, t, T->qhist[3], nullptr);
+      T->pf_entries += (int64_t)t.size() / 3 - 1;
+      T->pf_instrs += (int64_t)x.prog_pf.size() / 2 - 1;
       T->pf_count++;
     } else {
       pf_static[j >> 5] |= 1u << (j & 31);
@@ -3936,6 +3943,13 @@ int mq_tapes_prefilter_split(mq_tapes* T, int32_t* n_prefiltered, int32_t* ran) 
   return MQ_OK;
 }
 
+int mq_tapes_prefilter_entries(mq_tapes* T, int64_t* entries, int64_t* instrs) {
+  if (!T) return MQ_ERR_ARG;
+  if (entries) *entries = T->qsa_live ? T->pf_entries : 0;
+  if (instrs) *instrs = T->qsa_live ? T->pf_instrs : 0;
+  return MQ_OK;
+}
+
 int mq_tapes_prefilter_alive(mq_tapes* T, uint32_t* words, int64_t cap_words, int64_t* rows, int32_t* words_per_row,
                              int32_t* desc_tape, uint8_t* desc_has, int32_t cap_desc, int32_t* n_desc) {
   if (!T || !T->ctx) return MQ_ERR_ARG;
@@ -3975,7 +3989,7 @@ int mq_tape_prefilter_program(const mq_tape_batch* tb, int32_t t, uint32_t* word
 
 int mq_tapes_qsa_histogram(mq_tapes* T, int32_t which, int64_t* hist_out, int32_t cap, int64_t* pairs_out,
                            int32_t* n_kinds_out) {
-  if (!T || which < 0 || which > 2 || cap < 0) return MQ_ERR_ARG;
+  if (!T || which < 0 || which > 3 || cap < 0) return MQ_ERR_ARG;
   if (n_kinds_out) *n_kinds_out = QK_COUNT;
   const int n = std::min<int>(cap, QK_COUNT);
   const auto& h = T->qhist[which];

@@ -21,12 +21,15 @@ bool QsaTable::build(const std::vector<uint32_t> (&offsets)[2], const uint32_t (
     if (offsets[k].size() != (size_t)nh) return false;
     off[k] = offsets[k];
     hbase_lo[k] = base_lo[k];
-    kind_of[k].assign(1 << 16, -1);
+    // G's program words carry the handler word in 16 bits; P's entries carry absolute addresses,
+    // so only this table bounds P's handler area (1 MB; the fused narrow handlers end past 256 KB)
+    const uint32_t reach = k == 0 ? kQsaWordReachP : (1u << 16);
+    kind_of[k].assign(reach, -1);
     for (int h = 0; h < nh; h++)
-      if (hword(k, off[k][h]) < (1u << 16)) kind_of[k][hword(k, off[k][h])] = (int16_t)keys[h].kind;
+      if (hword(k, off[k][h]) < reach) kind_of[k][hword(k, off[k][h])] = (int16_t)keys[h].kind;
     uint32_t max_off = 0;
     for (int h = 0; h < nh; h++) {
-      ok = ok && off[k][h] != 0xFFFFFFFFu && hword(k, off[k][h]) < (1u << 16) &&
+      ok = ok && off[k][h] != 0xFFFFFFFFu && hword(k, off[k][h]) < reach &&
            (off[k][h] & ((k == 1 ? (1u << kQsaHandlerShiftG) : 4u) - 1)) == 0;
       max_off = std::max(max_off, off[k][h]);
     }
@@ -54,7 +57,7 @@ void qsa_count(const QsaTable& qt, int k, const std::vector<uint32_t>& tr, std::
   if (pairs && pairs->size() != (size_t)QK_COUNT * QK_COUNT) pairs->assign((size_t)QK_COUNT * QK_COUNT, 0);
   int prev = -1;
   for (size_t i = 0; i < tr.size();) {
-    const uint32_t key = k == 0 ? ((tr[i] - qt.hbase_lo[0]) >> 2) & 0xFFFFu : tr[i] & 0xFFFFu;
+    const uint32_t key = k == 0 ? ((tr[i] - qt.hbase_lo[0]) >> 2) & (kQsaWordReachP - 1) : tr[i] & 0xFFFFu;
     const int kind = qt.kind_of[k].empty() ? -1 : qt.kind_of[k][key];
     i += k == 0 ? 3 : 1;
     if (kind < 0) continue;
@@ -772,18 +775,88 @@ bool qsa_translate(const QsaTable& qt, const ModelLayout& ml, int k, bool models
 // A tape's low-limb prefilter program (CompiledTape::prog_pf) as P entries for frame mode 4:
 // (handler address, the instruction's 32-bit immediate, 0).  PUSH_VAR and the bitwise ops are
 // P's own handlers (on the narrow register map they act on eight blocks' low limbs).
+// A PUSH_VAR read by the very next instruction is not an entry of its own: the reader's fused
+// form takes the variable's registers in place (gen_qsa.py, the fused narrow handlers)
+//   PUSH_VAR v1; PUSH_VAR v2; binop  ->  kind32VV / B*VV (x, v1), imm = 8 * v2
+//   PUSH_VAR v; binop / EQ           ->  kind32V / B*V / EQ32V (d, v)
+//   PUSH_VAR v; opK / EQK            ->  kindK32V (d, v), imm = k
+// and a pattern whose handler the table lacks stays unfused.  MQ_PF_FUSE=0 (read per
+// translation) turns the peephole off: one entry per instruction.
 bool qsa_translate_pf(const QsaTable& qt, const CompiledTape& x, std::vector<uint32_t>& out) {
   out.clear();
   if (x.depth_pf > kQsaStackP) return false;
-  for (size_t pc = 0; pc + 1 < x.prog_pf.size(); pc += 2) {
-    const uint32_t op = x.prog_pf[pc] & 0xFFu, imm = x.prog_pf[pc + 1];
-    const int d = (int)((x.prog_pf[pc] >> 8) & 0xFu);
+  const char* fe = std::getenv("MQ_PF_FUSE");
+  const bool fuse = !(fe && fe[0] == '0' && fe[1] == 0);
+  const size_t n = x.prog_pf.size() / 2;
+  auto op_at = [&](size_t i) { return x.prog_pf[2 * i] & 0xFFu; };
+  auto d_at = [&](size_t i) { return (int)((x.prog_pf[2 * i] >> 8) & 0xFu); };
+  auto imm_at = [&](size_t i) { return x.prog_pf[2 * i + 1]; };
+  auto emit = [&](int kind, int d, int v, uint32_t im) -> bool {
+    if (d < 0 || d >= kQsaStackP || v < -1 || v >= kQsaVars) return false;
+    const int h = qt.index[0][kind][d][v + 1];
+    if (h < 0) return false;
+    out.push_back(qt.hbase_lo[0] + qt.off[0][h]);
+    out.push_back(im);
+    out.push_back(0);
+    return true;
+  };
+  // fused kinds of a reader whose right operand / both operands / only operand is a variable
+  auto kind_v = [](uint32_t op) -> int {
+    switch (op) {
+      case PF_ADD: return QK_ADD32V;
+      case PF_SUB: return QK_SUB32V;
+      case PF_MUL: return QK_MUL32V;
+      case PF_BAND: return QK_BANDV;
+      case PF_BOR: return QK_BORV;
+      case PF_BXOR: return QK_BXORV;
+      case PF_EQ: return QK_EQ32V;
+      default: return -1;
+    }
+  };
+  auto kind_vv = [](uint32_t op) -> int {
+    switch (op) {
+      case PF_ADD: return QK_ADD32VV;
+      case PF_SUB: return QK_SUB32VV;
+      case PF_MUL: return QK_MUL32VV;
+      case PF_BAND: return QK_BANDVV;
+      case PF_BOR: return QK_BORVV;
+      case PF_BXOR: return QK_BXORVV;
+      default: return -1;
+    }
+  };
+  auto kind_kv = [](uint32_t op) -> int {
+    switch (op) {
+      case PF_ADDK: return QK_ADDK32V;
+      case PF_MULK: return QK_MULK32V;
+      case PF_ANDK: return QK_ANDK32V;
+      case PF_ORK: return QK_ORK32V;
+      case PF_XORK: return QK_XORK32V;
+      case PF_EQK: return QK_EQK32V;
+      default: return -1;
+    }
+  };
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t op = op_at(i), imm = imm_at(i);
+    const int d = d_at(i);
     int kind = -1, v = -1;
     uint32_t im = imm;
     switch (op) {
       case PF_END: kind = QK_END; break;
       case PF_PUSH_VAR:
         if (imm >= (uint32_t)kQsaVars) return false;
+        if (fuse && i + 2 < n && op_at(i + 1) == PF_PUSH_VAR && d_at(i + 1) == d + 1 && imm_at(i + 1) < (uint32_t)kQsaVars &&
+            d_at(i + 2) == d + 1 && kind_vv(op_at(i + 2)) >= 0 && emit(kind_vv(op_at(i + 2)), d, (int)imm, 8u * imm_at(i + 1))) {
+          i += 2;
+          continue;
+        }
+        if (fuse && i + 1 < n && d_at(i + 1) == d) {
+          const uint32_t nop = op_at(i + 1);
+          if ((kind_v(nop) >= 0 && emit(kind_v(nop), d, (int)imm, 0)) ||
+              (kind_kv(nop) >= 0 && emit(kind_kv(nop), d, (int)imm, imm_at(i + 1)))) {
+            i += 1;
+            continue;
+          }
+        }
         kind = QK_PUSH_VAR, v = (int)imm, im = 0;
         break;
       case PF_PUSH_K: kind = QK_PUSH_K32; break;
@@ -804,12 +877,7 @@ bool qsa_translate_pf(const QsaTable& qt, const CompiledTape& x, std::vector<uin
       case PF_EQK: kind = QK_EQK32; break;
       default: return false;
     }
-    if (d >= kQsaStackP) return false;
-    const int h = qt.index[0][kind][kind == QK_END ? 0 : d][v + 1];
-    if (h < 0) return false;
-    out.push_back(qt.hbase_lo[0] + qt.off[0][h]);
-    out.push_back(im);
-    out.push_back(0);
+    if (!emit(kind, kind == QK_END ? 0 : d, v, im)) return false;
   }
   return !out.empty();
 }

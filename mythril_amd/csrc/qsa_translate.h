@@ -21,6 +21,12 @@ constexpr int kQsaMaxTemps = 16;
 // Handler byte offset -> the 16-bit word field that encodes it: P / G handlers are 4-byte
 // aligned (shift 2); the diagnostic G profile build aligns them to 8 bytes (shift 3, 512 KB reach)
 inline uint32_t hword(int k, uint32_t off) { return off >> (k == 1 ? kQsaHandlerShiftG : 2); }
+// P entries hold absolute handler addresses, so nothing in the kernel bounds P's handler area;
+// the host's word -> kind table (QsaTable::kind_of, histograms) does: 2^18 four-byte words = 1 MB
+// of handlers.  With the fused narrow handlers the last P handler starts 267 684 bytes (261 KB)
+// behind the handler base.  A handler past the bound makes QsaTable::build return false: the
+// assembly interpreters do not come up, nothing runs wrong.
+constexpr uint32_t kQsaWordReachP = 1u << 18;
 
 // The handler table of the assembly interpreters; k = 0 the P kernel, k = 1 the G kernel.
 struct QsaTable {

@@ -91,6 +91,7 @@ def load_library(path: str = LIB_PATH):
         L.mq_tape_prefilter_program.argtypes = [C.POINTER(MqTapeBatch), C.c_int32, C.POINTER(C.c_uint32), C.c_int32,
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.mq_tapes_prefilter_split.argtypes = [P] + [C.POINTER(C.c_int32)] * 2
+        L.mq_tapes_prefilter_entries.argtypes = [P] + [C.POINTER(C.c_int64)] * 2
         L.mq_tapes_prefilter_alive.argtypes = [P, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int32)]
         L.mq_tapes_upload_dag.argtypes =[P, C.POINTER(MqDagBatch), C.POINTER(P), C.POINTER(C.c_int32)]
@@ -335,7 +336,8 @@ class CompiledTapes:
 
     def handler_histogram(self, which: int = 1, pairs: bool = False, wait_variants: bool = False):
         """After a launch: {handler kind: dispatches per (tape, model) pair, summed over tapes} of
-        the assembly translation (which = 0 P tapes, 1 G tapes, 2 G column programs); with
+        the assembly translation (which = 0 P tapes, 1 G tapes, 2 G column programs, 3 the P
+        tapes' low-limb prefilter programs, dispatches per (tape, 512-model wave tile)); with
         pairs, also {(kind, next kind): count} over the G tapes.  A G stack reader's "_L" variant
         (waits for LDS / scalar loads only, gen_qsa.py LGKMWAIT) counts as its kind unless
         ``wait_variants``.  Diagnostic."""
@@ -374,6 +376,13 @@ class CompiledTapes:
         n, ran = C.c_int32(), C.c_int32()
         _check(self.ev.lib.mq_tapes_prefilter_split(self.handle, C.byref(n), C.byref(ran)), "mq_tapes_prefilter_split")
         return n.value, bool(ran.value)
+
+    def prefilter_entries(self):
+        """(entries of the prefilter programs' translation, instructions of the compiled programs),
+        summed over the tapes prefilter_split counts, END left out (mq_tapes_prefilter_entries)."""
+        e, i = C.c_int64(), C.c_int64()
+        _check(self.ev.lib.mq_tapes_prefilter_entries(self.handle, C.byref(e), C.byref(i)), "mq_tapes_prefilter_entries")
+        return e.value, i.value
 
     def prefilter_alive(self):
         """Diagnostic, after a launch that ran the prefilter: (bits, tapes, has) -- bits[b, d]

@@ -6,7 +6,8 @@ dispatch tail) and times each body in a loop at 1, 2, 4 and 8 waves per SIMD, so
 rate of a body is measured apart from the interpreter's dispatch:
   cycles per wave-instruction at occupancy W = elapsed cycles / (bodies per wave * VALU per body)
 and the same for a body preceded by the P dispatch's scalar program-entry load (s_load + wait).
-usage: python tools/issue_probe.py build   (here)   |   tools/_issue_probe   (on the GPU box)
+usage: python tools/issue_probe.py build [BODY ...]   (all bodies, or the named ones only)
+       tools/_issue_probe                              (on the GPU box)
 """
 import os
 import subprocess
@@ -60,6 +61,11 @@ INDEP = {
     "i_cndmask": "v_cndmask_b32_e64 {d}, {a}, {b}, s[60:61]",
     "i_fma_f32": "v_fma_f32 {d}, {a}, {b}, {c}",
     "i_readlane": "v_readlane_b32 s{sl}, {a}, 3",
+    # packed 16-bit integer ops (VOP3P): two 16-bit blocks a VGPR lane, the rate that decides a
+    # 1 024-model narrow dispatch
+    "i_pk_add_u16": "v_pk_add_u16 {d}, {a}, {b}",
+    "i_pk_sub_u16": "v_pk_sub_u16 {d}, {a}, {b}",
+    "i_pk_mullo_u16": "v_pk_mul_lo_u16 {d}, {a}, {b}",
 }
 
 
@@ -111,7 +117,9 @@ def main():
     src = ["#include <hip/hip_runtime.h>", "#include <cstdio>",
            "#define CHK(x) do { hipError_t e = (x); if (e != hipSuccess) { fprintf(stderr, \"%s\\n\", hipGetErrorString(e)); return 1; } } while (0)"]
     runs = []
-    for name in BODIES:
+    only = [a for a in sys.argv[1:] if a != "build"]
+    assert all(a in BODIES for a in only), f"bodies: {BODIES}"
+    for name in (only or BODIES):
         for smem in ((0,) if name in INDEP else (0, 1, 2, 3, 4)):
             nvalu, text = kernel(name, smem)
             src.append(text)

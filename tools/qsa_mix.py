@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Handler-kind mix of the assembly translation of a bench workload (diagnostic): dispatches per
-(tape, model) pair by kind and the most frequent (kind, next kind) pairs of the G tapes."""
+(tape, model) pair by kind -- the narrow mix of the low-limb prefilter programs among them, with
+their entries per program (MQ_PF_FUSE=0: unfused) -- and the most frequent (kind, next kind)
+pairs of the G tapes."""
 import os
 import sys
 
@@ -17,7 +19,11 @@ ev.upload_models(mb)
 ct = ev.compile(tb)
 ev.first_hit(ct)
 print("split", ct.asm_split(), "columns", ct.column_asm_split())
-for which, name in ((0, "P tapes"), (1, "G tapes"), (2, "G columns")):
+n_pf, ran = ct.prefilter_split()
+entries, instrs = ct.prefilter_entries()
+print("prefilter", (n_pf, ran), f"entries {entries} of {instrs} instructions"
+      + (f" ({entries / n_pf:.2f} of {instrs / n_pf:.2f} a program)" if n_pf else ""))
+for which, name in ((0, "P tapes"), (1, "G tapes"), (2, "G columns"), (3, "prefilter programs (narrow, per 512 models)")):
     h = ct.handler_histogram(which)
     tot = sum(h.values())
     print(f"== {name}: {tot} dispatches per model")
